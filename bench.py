@@ -14,12 +14,19 @@ process before this process touches a GPU.  Each rank codes its own 2^30-symbol 
 (weak scaling, no collective on the data path).
 
 value = total uncompressed symbol GiB of all ranks / (max-over-ranks time per step).
+
+A plain run does only what that figure needs: set-up, a clock-settling pre-roll of the same
+round trips, the warm-up, the `--steps` timed steps (ms_per_step = their wall time / steps),
+the round-trip check, and one JSON line.  `--dump-outputs DIR` also writes what the last timed
+step computed (dump_outputs).  Everything below runs only with `--full` (the --no-* options
+then leave single parts out):
+
 roofline: algorithmic bytes of the dominant kernel (n*w symbols + compressed stream
 bytes) / its average launch time from HIP events on its stream.
 cpu_baseline: the oracle (oracle/ans_oracle.c) timed on a bounded sample of the same
 workload (rank 0, N=1 only).
 
-Sub-objects outside the headline's timed region:
+Sub-objects outside the headline's timed region (`--full`):
   c4    BASELINE.json configs[3] per rank (2^29 u16 symbols, 65,536-symbol table): at N=8
         the aggregate is exactly C4's 8 GiB over 8 GPUs.  Its own barrier-bracketed wall
         clock and HIP events; the decoder's L2 request rate against tools/l2rand.hip's ceiling.
@@ -66,6 +73,11 @@ def parse(argv=None):
     p.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     p.add_argument("--log2n", type=int, default=None, help="symbols per rank = 2^log2n (default: the config's)")
     p.add_argument("--chunk-len", type=int, default=4096)
+    p.add_argument("--full", action="store_true",
+                   help="also the roofline, the dense, c4 and host sub-objects and the CPU baseline "
+                        "(a plain run times the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed to DIR/<name>.npy")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-dense", action="store_true", help="skip the dense-container pass")
@@ -75,7 +87,10 @@ def parse(argv=None):
     p.add_argument("--strong", action="store_true",
                    help="strong scaling: the config's 2^log2n symbols in total, split over the ranks")
     p.add_argument("--test-fail-rank", type=int, default=None, help=argparse.SUPPRESS)  # tests/test_bench.py only
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -329,6 +344,58 @@ def dense_pass(ctx, gt, syms, sym_bytes, n, L, nchunks, slots, cap, steps, warmu
     return finish
 
 
+def settle_pass(ctx, gt, syms, sym_bytes, n, L, slots, cap, lens, out, steps, warmup):
+    """The plain run's clock-settling pre-roll: as many untimed round trips of the headline's own
+    step as the dense pass queues in the same place under --full (~50 ms of continuous work
+    at least, the clocks' settling time), with no host synchronisation before the warm-up."""
+    for _ in range(max(warmup, 20) + min(steps, 10)):
+        gt.dev_encode(syms, sym_bytes, n, L, slots, cap, lens, ctx.status, ctx.stream)
+        gt.dev_decode(slots, None, cap, lens, n, L, out, sym_bytes, ctx.status, ctx.stream)
+
+
+DUMP_SEED = 0x5EED  # the sample positions of dump_outputs: the same for every run and build
+DUMP_SYMBOLS = 1 << 21  # decoded symbols kept (8 MiB as float32)
+DUMP_LENS = 1 << 20  # chunk lengths kept (4 MiB; float64 only where a slot holds 2^24 bytes or more)
+DUMP_STREAM_BYTES = 6 << 20  # stream bytes kept, whole slots (24 MiB as float32)
+
+
+def dump_outputs(ctx, path, slots, cap, lens, out, sym_bytes, n, nchunks):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as
+    DIR/<name>.npy (rank 0; other ranks write <name>.rank<r>.npy), under 64 MB in all:
+      lens     every chunk's stream length in bytes (float32), or, of more than DUMP_LENS chunks,
+               those of the sampled chunks
+      stream   the encoded streams of a sample of chunks, one row of slot_cap byte values per
+               chunk (float32), zero past the chunk's length (those slot bytes are never written)
+      stream_chunks  the sampled chunk numbers (float64), ascending
+      symbols  the decoded symbols (float32; float64 for 4-byte symbols), all of them or those
+               at a sample of positions
+    Samples are numpy RandomState(DUMP_SEED) draws (a frozen stream), sorted: first the chunk
+    numbers, then the symbol positions.  The inputs are a function of the arguments alone
+    (counter-based generator), so two builds run with the same arguments compare file for file."""
+    torch = ctx.torch
+    os.makedirs(path, exist_ok=True)
+    rs = np.random.RandomState(DUMP_SEED)
+    k = max(1, min(nchunks, DUMP_STREAM_BYTES // max(cap, 1)))
+    chunks = np.arange(nchunks, dtype=np.int64) if k == nchunks else np.sort(rs.randint(0, nchunks, size=k, dtype=np.int64))
+    pos = np.arange(n, dtype=np.int64) if n <= DUMP_SYMBOLS else np.sort(rs.randint(0, n, size=DUMP_SYMBOLS, dtype=np.int64))
+    d_chunks = torch.from_numpy(chunks).cuda()
+    d_lens = lens[d_chunks].to(torch.int64)
+    rows = slots.view(nchunks, cap)[d_chunks]
+    rows = torch.where(torch.arange(cap, device="cuda")[None, :] < d_lens[:, None], rows, torch.zeros_like(rows))
+    sym = out[torch.from_numpy(pos).cuda()].cpu().numpy()
+    sym = sym.view({1: np.uint8, 2: np.uint16, 4: np.uint32}[sym_bytes])
+    arrays = {
+        "lens": (lens if nchunks <= DUMP_LENS else d_lens).cpu().numpy().astype(np.float32 if cap < 1 << 24 else np.float64),
+        "stream": rows.cpu().numpy().astype(np.float32),
+        "stream_chunks": chunks.astype(np.float64),
+        "symbols": sym.astype(np.float64 if sym_bytes == 4 else np.float32),
+    }
+    assert sum(a.nbytes for a in arrays.values()) < 64e6
+    suffix = "" if ctx.rank == 0 else f".rank{ctx.rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+
+
 def kernel_name(A, gt, which, sym_bytes):
     if which == "decode":
         return "k_decode" + {"global": "_g", "wide": "_w"}.get(gt.decode_kernel(sym_bytes), "")
@@ -576,8 +643,14 @@ def main():
     # headline 2.5% below its steady state (497 vs 511 GiB/s at --warmup 30 on one box; queued
     # this way, 513 at either).
     # (20 warm-up steps of its own at least: ~50 ms, the clocks' settling time)
-    pre = None if args.no_dense else (lambda: dense_pass(ctx, gt, syms, sym_bytes, n, L, nchunks, slots, cap,
-                                                         min(args.steps, 10), max(args.warmup, 20)))
+    # A plain run queues as many of the headline's own round trips in its place (settle_pass).
+    if not args.full:
+        pre = lambda: settle_pass(ctx, gt, syms, sym_bytes, n, L, slots, cap, lens, out, args.steps, args.warmup)  # noqa: E731
+    elif args.no_dense:
+        pre = None
+    else:
+        pre = (lambda: dense_pass(ctx, gt, syms, sym_bytes, n, L, nchunks, slots, cap,
+                                  min(args.steps, 10), max(args.warmup, 20)))
     elapsed, enc_ms, dec_ms, dense_finish = timed_round_trips(ctx, gt, syms, sym_bytes, n, L, slots, cap, lens,
                                                               out, args.steps, args.warmup, pre=pre,
                                                               fail_rank=args.test_fail_rank)
@@ -593,11 +666,18 @@ def main():
         comp_bytes = int(lens.to(torch.int64).sum().item())
     except Exception:  # noqa: BLE001
         bad = 1.0
+    if args.dump_outputs:
+        err = None
+        try:
+            dump_outputs(ctx, args.dump_outputs, slots, cap, lens, out, sym_bytes, n, nchunks)
+        except Exception as e:  # noqa: BLE001
+            err = e
+        ctx.agree(err, "--dump-outputs")
     del slots, out
     torch.cuda.empty_cache()
 
     c4, c4_row = None, None
-    if args.config != "c4" and not args.no_c4:
+    if args.full and args.config != "c4" and not args.no_c4:
         c4_row, c4_names, c4_n, c4_masses = c4_pass(ctx, args)  # [elapsed, enc_ms, dec_ms, comp, bad]
 
     # every rank's [elapsed, bad, enc_ms, dec_ms, n, comp_bytes] (+ its c4 row)
@@ -608,16 +688,56 @@ def main():
     if c4_row is not None:
         c4 = c4_summary([r[6:] for r in rows], c4_names, c4_n, c4_masses, args, world)
 
+    wall = max(r[0] for r in rows)
+    ms_per_step = 1e3 * wall / args.steps
+    total_sym_bytes = total_n * sym_bytes
+    value = total_sym_bytes / (wall / args.steps) / 2**30
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (counter-based splitmix64 iid symbols generated on device, SURVEY.md §8d)",
+        "config": {
+            "workload": f"{args.config.upper()}: 2^{log2n} iid u{8 * sym_bytes} symbols "
+                        f"{'in total' if args.strong else 'per GPU'}, "
+                        f"{len(masses)}-symbol Categorical (norm {int(masses.sum())}), chunk_len {L}",
+            "symbols_per_gpu": n,
+            "symbols_per_rank": [int(r[4]) for r in rows],
+            "symbols_total": total_n,
+            "symbol_bytes": sym_bytes,
+            "chunk_len": L,
+            "chunks_per_gpu": nchunks,
+            "parallelism": f"chunk-sharded x{world}, no collective",
+        },
+        "per_rank_ms_per_step": {"min": round(1e3 * min(r[0] for r in rows) / args.steps, 4),
+                                 "max": round(ms_per_step, 4)},
+        "encode_ms": round(enc_ms, 4),
+        "decode_ms": round(dec_ms, 4),
+        "encode_gib_s": round(n * sym_bytes / (enc_ms * 1e-3) / 2**30, 3),
+        "decode_gib_s": round(n * sym_bytes / (dec_ms * 1e-3) / 2**30, 3),
+        "compressed_bytes_per_symbol": round(comp_bytes / n, 5),
+        "parity": "round trip verified on device; byte parity vs the oracle: tests/test_gpu_parity.py",
+    }
+    if not args.full:  # the plain run ends here: the headline and what its own timed steps gave
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     host = None
     if world == 1 and not args.no_host and args.config in ("c3", "c3p2", "c3s", "c3b"):
         host = host_pass(ctx, gt, syms, n, L)
         if not host.pop("ok"):
             raise SystemExit("host-memory round trip failed")
-
-    wall = max(r[0] for r in rows)
-    ms_per_step = 1e3 * wall / args.steps
-    total_sym_bytes = total_n * sym_bytes
-    value = total_sym_bytes / (wall / args.steps) / 2**30
 
     dom_name, dom_ms = ("decode", dec_ms) if dec_ms >= enc_ms else ("encode", enc_ms)
     dom_kernel = kernel_name(A, gt, dom_name, sym_bytes)
@@ -669,41 +789,10 @@ def main():
     if rank == 0:
         per_frac = [(r[4] * sym_bytes + r[5]) / (max(r[2], r[3]) * 1e-3) / 1e9 / HBM_PEAK_GBS for r in rows]
         line = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if args.strong else "weak",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic (counter-based splitmix64 iid symbols generated on device, SURVEY.md §8d)",
-            "config": {
-                "workload": f"{args.config.upper()}: 2^{log2n} iid u{8 * sym_bytes} symbols "
-                            f"{'in total' if args.strong else 'per GPU'}, "
-                            f"{len(masses)}-symbol Categorical (norm {int(masses.sum())}), chunk_len {L}",
-                "symbols_per_gpu": n,
-                "symbols_per_rank": [int(r[4]) for r in rows],
-                "symbols_total": total_n,
-                "symbol_bytes": sym_bytes,
-                "chunk_len": L,
-                "chunks_per_gpu": nchunks,
-                "parallelism": f"chunk-sharded x{world}, no collective",
-            },
-            "per_rank_ms_per_step": {"min": round(1e3 * min(r[0] for r in rows) / args.steps, 4),
-                                     "max": round(ms_per_step, 4)},
-            "encode_ms": round(enc_ms, 4),
-            "decode_ms": round(dec_ms, 4),
-            "encode_gib_s": round(n * sym_bytes / (enc_ms * 1e-3) / 2**30, 3),
-            "decode_gib_s": round(n * sym_bytes / (dec_ms * 1e-3) / 2**30, 3),
-            "compressed_bytes_per_symbol": round(comp_bytes / n, 5),
+            **head,
             "dense": dense,
             "c4": c4,
             "host": host,
-            "parity": "round trip verified on device; byte parity vs the oracle: tests/test_gpu_parity.py",
             "roofline": {
                 "bound": bound,
                 "kernel": dom_kernel,

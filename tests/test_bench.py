@@ -26,7 +26,7 @@ def test_bench_launches_two_ranks_itself():
     env = dict(os.environ, BENCH_SHARE_DEVICE="1", BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "-u", BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "24",
+    cmd = [sys.executable, "-u", BENCH, "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "24",
            "--c4-log2n", "22", "--no-cpu-baseline", "--no-dense", "--no-host"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=110, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -85,8 +85,8 @@ def test_bench_eight_ranks_one_device():
     ranks (global symbol offsets 0..7 x 2^20, the same rank order and shard layout as on an 8-GPU
     node), rank 0 prints one JSON line with eight per-rank entries and the C4 sub-object's
     per-rank spread; gloo carries the barrier and the gather (RCCL needs a GPU per rank)."""
-    r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "8", "--steps", "3", "--warmup", "1", "--log2n", "20",
-                        "--c4-log2n", "18", "--no-cpu-baseline", "--no-dense", "--no-host"],
+    r = subprocess.run([sys.executable, "-u", BENCH, "--full", "--gpus", "8", "--steps", "3", "--warmup", "1",
+                        "--log2n", "20", "--c4-log2n", "18", "--no-cpu-baseline", "--no-dense", "--no-host"],
                        env={k: v for k, v in dict(os.environ, BENCH_SHARE_DEVICE="1", BENCH_BACKEND="gloo").items()
                             if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")},
                        capture_output=True, text=True, timeout=280, cwd=ROOT)
@@ -121,3 +121,65 @@ def test_c4_l2_share_follows_the_staged_bucket_width():
     assert abs(share - 0.8174) < 1e-3
     # a table whose buckets all fit in LDS at the fine width serves every lookup from LDS
     assert bench.c4_l2_share(np.full(300, 20, dtype=np.uint64)) == 0.0  # norm 6,000: 6,000 buckets
+
+
+def test_plain_and_full_options_parse():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line only (no sub-object
+    that takes a run of its own), and --dump-outputs writes what the timed path's last step left:
+    every file checked against the oracle on the same workload at the documented sample positions
+    (2^22 symbols: more than DUMP_SYMBOLS, and more chunks than fit DUMP_STREAM_BYTES, so both
+    samples are drawn)."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "shuffle-coding_amd"))
+    import numpy as np
+
+    import ans_amd as A
+    import bench
+    from oracle import oracle as orc
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", "22",
+                        "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=110, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "GiB/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - (1 << 22) / (d["ms_per_step"] * 1e-3) / 2**30) < 0.01 * d["value"]
+    assert not {"dense", "c4", "host", "roofline", "cpu_baseline"} & set(d)
+
+    n, L = 1 << 22, 4096
+    masses_name, _, sym_bytes, seed = bench.CONFIGS["c3"]
+    masses = getattr(A, masses_name)()
+    syms = orc.gen_iid(masses, seed, 0, n)
+    odata, ooffs, olens = orc.encode_chunks(masses, syms, L)
+    got = {os.path.basename(p)[:-4]: np.load(p) for p in sorted(out.glob("*.npy"))}
+    assert sorted(got) == ["lens", "stream", "stream_chunks", "symbols"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    nchunks = n // L
+    rs = np.random.RandomState(bench.DUMP_SEED)
+    k = got["stream"].shape[0]
+    assert 1 <= k < nchunks and k * got["stream"].shape[1] <= bench.DUMP_STREAM_BYTES
+    chunks = np.sort(rs.randint(0, nchunks, size=k, dtype=np.int64))
+    pos = np.sort(rs.randint(0, n, size=bench.DUMP_SYMBOLS, dtype=np.int64))
+    assert np.array_equal(got["stream_chunks"], chunks)
+    assert np.array_equal(got["lens"], olens.astype(np.float64))
+    assert np.array_equal(got["symbols"], syms[pos].astype(np.float64))
+    for row, c in zip(got["stream"], chunks):
+        ln = int(olens[c])
+        assert np.array_equal(row[:ln], odata[int(ooffs[c]):int(ooffs[c]) + ln]) and not row[ln:].any()

@@ -8,9 +8,9 @@ export TMPDIR=/tmp
 OUT=gpurun_out/wide_${TAG}
 mkdir -p $OUT
 for cfg in c4 c4s c4b; do
-  timeout -k 10 300 python3 bench.py --config $cfg --steps 20 --warmup 5 --no-c4 --no-host --no-dense --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { tail -5 $OUT/bench_$cfg.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-c4 --no-host --no-dense --no-cpu-baseline > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { tail -5 $OUT/bench_$cfg.err; exit 1; }
   python3 -c "import json,sys; d=json.loads(open('$OUT/bench_$cfg.json').read().strip().splitlines()[-1]); print('$cfg', d['value'], d['encode_ms'], d['decode_ms'], d['roofline']['kernel'])"
-  timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $OUT/stats_$cfg -o run --output-format csv -- python3 bench.py --config $cfg --steps 20 --warmup 5 --no-c4 --no-host --no-dense --no-cpu-baseline > $OUT/stats_$cfg.log 2>&1 || exit 1
+  timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $OUT/stats_$cfg -o run --output-format csv -- python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-c4 --no-host --no-dense --no-cpu-baseline > $OUT/stats_$cfg.log 2>&1 || exit 1
   python3 tools/kstats_json.py $OUT/stats_$cfg/run_kernel_stats.csv $OUT/kstats_$cfg.json --config $cfg --log2n 29 --trace $OUT/stats_$cfg/run_kernel_trace.csv --skip 5 --count 20 || exit 1
 done
 echo done

@@ -1,7 +1,7 @@
 # rocprofv3 PMC passes over one command (one counter group per pass, --kernel-trace only;
 # never combined with sys/runtime traces).  The memory-side byte counts come from the TCC's
 # request-size counters (MI355X_MICROARCH.md §HBM; tools/pmc_summary.py explains the sums).
-# usage: bash tools/pmc.sh <tag> <command...>     (e.g. python3 bench.py --steps 2 --warmup 1)
+# usage: bash tools/pmc.sh <tag> <command...>     (e.g. python3 bench.py --full --steps 2 --warmup 1)
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 TAG=${1:-pmc}; shift

@@ -3,12 +3,13 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
-mkdir -p gpurun_out/pmcw_$1
-timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_INSTS_SALU -d gpurun_out/pmcw_$1 -o run --output-format csv -- python3 bench.py --config $2 --steps 2 --warmup 1 --no-cpu-baseline --no-dense --no-c4 --no-host > gpurun_out/pmcw_$1/log 2>&1
-rc=$?; echo "pmc rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/pmcw_$1/log; exit $rc; }
-python3 - $1 <<'PY'
+OUT=${OUT:-bench_out}  # where the logs and result lines go
+mkdir -p $OUT/pmcw_$1
+timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_INSTS_SALU -d $OUT/pmcw_$1 -o run --output-format csv -- python3 bench.py --full --config $2 --steps 2 --warmup 1 --no-cpu-baseline --no-dense --no-c4 --no-host > $OUT/pmcw_$1/log 2>&1
+rc=$?; echo "pmc rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/pmcw_$1/log; exit $rc; }
+python3 - $1 $OUT <<'PY'
 import csv, glob, sys, collections
-f = glob.glob(f"gpurun_out/pmcw_{sys.argv[1]}/**/*counter_collection.csv", recursive=True)[0]
+f = glob.glob(f"{sys.argv[2]}/pmcw_{sys.argv[1]}/**/*counter_collection.csv", recursive=True)[0]
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
 for r in csv.DictReader(open(f)):
     k = r["Kernel_Name"].split("<")[0][-40:]
