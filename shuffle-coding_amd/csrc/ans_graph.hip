@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "ans_ctx.hpp"
+#include "ans_hostio.hpp"
+#include "ans_scan.hpp"
 
 namespace {
 
@@ -118,29 +120,7 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_count(const uint8_t* __re
     }
 }
 
-// pass 2: exclusive scan of the tile counts (one workgroup, contiguous segments per thread)
-__global__ __launch_bounds__(1024) void k_tile_scan(const uint32_t* __restrict__ counts, uint64_t ntiles,
-                                                    uint64_t* __restrict__ base, uint64_t* __restrict__ total) {
-    __shared__ uint64_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint64_t per = (ntiles + 1023) / 1024, b = t * per, e = b + per < ntiles ? b + per : ntiles;
-    uint64_t sum = 0;
-    for (uint64_t i = b; i < e; ++i) sum += counts[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint64_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - sum;
-    for (uint64_t i = b; i < e; ++i) {
-        base[i] = run;
-        run += counts[i];
-    }
-    if (t == 1023) *total = part[1023];
-}
+// pass 2: exclusive scan of the tile counts into base, their total apart (k_excl_scan, ans_scan.hpp)
 
 // pass 3: each set slot becomes its edge at base[tile] + (set slots before it in the tile)
 __global__ __launch_bounds__(kTileThreads) void k_tile_emit(EdgeSpace es, const uint8_t* __restrict__ dense,
@@ -451,15 +431,6 @@ int scratch(ans_gpu* g, size_t bytes, void** out) {
 
 bool valid_space(uint64_t n) { return n < (1ull << 32); }
 
-// Device buffer released at scope exit (host-level graph calls only).
-struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess; }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
-
 }  // namespace
 
 extern "C" {
@@ -509,7 +480,7 @@ int ans_dev_dense_to_edges(ans_gpu* g, uint64_t num_nodes, int directed, int loo
     auto* counts = reinterpret_cast<uint32_t*>(base + ntiles);
     k_tile_count<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(d_dense, len, counts);
     HIP_TRY(hipGetLastError());
-    k_tile_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_count);
+    k_excl_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_count);
     HIP_TRY(hipGetLastError());
     k_tile_emit<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(e, d_dense, len, base, d_edges, cap, d_status);
     HIP_TRY(hipGetLastError());
@@ -535,10 +506,12 @@ int ans_gpu_dense_set_encode(ans_gpu_table* gt, uint64_t num_nodes, int directed
     const hipStream_t s = g->stream;
     uint64_t slot_cap = 0;
     ans_gpu_slot_capacity(gt, chunk_len, &slot_cap);
-    Buf d_dense, d_edges, d_status, d_slots, d_lens, d_offs, d_out;
-    if (!d_dense.alloc(len + 16) || !d_edges.alloc(8 * num_edges) || !d_status.alloc(16) ||
-        !d_slots.alloc(nchunks * slot_cap) || !d_lens.alloc(4 * nchunks) || !d_offs.alloc(8 * nchunks))
-        return ANS_E_DEVICE;
+    DevBuf d_dense, d_edges, d_status, d_slots, d_lens;
+    HIP_TRY(d_dense.alloc(len + 16));
+    HIP_TRY(d_edges.alloc(8 * num_edges));
+    HIP_TRY(d_status.alloc(16));
+    HIP_TRY(d_slots.alloc(nchunks * slot_cap));
+    HIP_TRY(d_lens.alloc(4 * nchunks));
     if (num_edges) HIP_TRY(hipMemcpyAsync(d_edges.p, edges, 8 * num_edges, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(d_status.p, 0, 4, s));
     int rc = ans_dev_edges_to_dense(g, num_nodes, directed, loops, d_edges.as<uint32_t>(), num_edges,
@@ -546,34 +519,9 @@ int ans_gpu_dense_set_encode(ans_gpu_table* gt, uint64_t num_nodes, int directed
     if (rc) return rc;
     rc = ans_dev_encode_chunks(gt, d_dense.p, 1, len, chunk_len, d_slots.as<uint8_t>(), slot_cap,
                                d_lens.as<uint32_t>(), d_status.as<uint32_t>(), s);
-    if (rc) return rc;
-    int st = 0;
-    if ((rc = ans_dev_status(g, d_status.as<uint32_t>(), s, &st))) return rc;
-    if (st) return st;
-    std::vector<uint32_t> hl(nchunks);
-    if (nchunks) HIP_TRY(hipMemcpy(hl.data(), d_lens.p, 4 * nchunks, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> off(nchunks);
-    uint64_t acc = 0;
-    for (uint64_t j = 0; j < nchunks; ++j) {
-        off[j] = acc;
-        acc += hl[j];
-    }
-    *total = acc;
-    if (!out) return ANS_OK;
-    if (out_cap < acc) return ANS_E_LEN;
-    for (uint64_t j = 0; j < nchunks; ++j) {
-        offsets[j] = off[j];
-        lens[j] = hl[j];
-    }
-    if (!acc) return ANS_OK;
-    if (!d_out.alloc(acc + 16)) return ANS_E_DEVICE;
-    HIP_TRY(hipMemcpyAsync(d_offs.p, off.data(), 8 * nchunks, hipMemcpyHostToDevice, s));
-    if ((rc = ans_dev_compact(g, d_slots.as<uint8_t>(), slot_cap, d_lens.as<uint32_t>(), d_offs.as<uint64_t>(), nchunks,
-                              d_out.as<uint8_t>(), s)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, acc, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ANS_OK;
+    if (rc || (rc = read_status(g, d_status.as<uint32_t>(), s))) return rc;
+    return download_container(g, d_slots.as<uint8_t>(), slot_cap, d_lens.as<uint32_t>(), nchunks, s, out, out_cap,
+                              offsets, lens, total);
 } ANS_CATCH
 
 // DenseSetIID::pop (src/graph_codec.rs:117-120), chunked: decodes the dense vector and
@@ -594,35 +542,28 @@ int ans_gpu_dense_set_decode(ans_gpu_table* gt, uint64_t num_nodes, int directed
     const hipStream_t s = g->stream;
     uint64_t slot_cap = 0, max_len = 0;
     ans_gpu_slot_capacity(gt, chunk_len, &slot_cap);
-    std::vector<uint32_t> l32(nchunks);
-    for (uint64_t j = 0; j < nchunks; ++j) {
-        if (lens[j] > 0xffffffffull || offsets[j] > in_len || lens[j] > in_len - offsets[j]) return ANS_E_LEN;
-        l32[j] = static_cast<uint32_t>(lens[j]);
-        max_len = std::max<uint64_t>(max_len, l32[j]);
-    }
-    slot_cap = std::max<uint64_t>(slot_cap, (max_len + 64 + 127) & ~uint64_t(127));
-    Buf d_in, d_offs, d_lens, d_slots, d_dense, d_status, d_edges, d_count;
-    if (!d_in.alloc(in_len + 16) || !d_offs.alloc(8 * nchunks) || !d_lens.alloc(4 * nchunks) ||
-        !d_slots.alloc(nchunks * slot_cap) || !d_dense.alloc(len + 16) || !d_status.alloc(16) ||
-        !d_edges.alloc(8 * cap) || !d_count.alloc(16))
-        return ANS_E_DEVICE;
-    if (in_len) HIP_TRY(hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, s));
-    if (nchunks) {
-        HIP_TRY(hipMemcpyAsync(d_offs.p, offsets, 8 * nchunks, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_lens.p, l32.data(), 4 * nchunks, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemsetAsync(d_status.p, 0, 4, s));
-    int rc = ans_dev_expand(g, d_in.as<uint8_t>(), d_offs.as<uint64_t>(), d_lens.as<uint32_t>(), nchunks,
-                            d_slots.as<uint8_t>(), slot_cap, s);
+    std::vector<uint32_t> l32;
+    int rc = narrow_lens(offsets, lens, nchunks, in_len, l32, &max_len);
     if (rc) return rc;
-    rc = ans_dev_decode_chunks(gt, d_slots.as<uint8_t>(), nullptr, slot_cap, d_lens.as<uint32_t>(), len, chunk_len,
-                               ANS_GEN_ZEROS, d_dense.p, 1, d_status.as<uint32_t>(), s);
+    slot_cap = std::max<uint64_t>(slot_cap, (max_len + 64 + 127) & ~uint64_t(127));
+    DevStreams d;
+    DevBuf d_slots, d_dense, d_edges, d_count;
+    if ((rc = upload_streams(in, in_len, offsets, l32, s, d))) return rc;
+    HIP_TRY(d_slots.alloc(nchunks * slot_cap));
+    HIP_TRY(d_dense.alloc(len + 16));
+    HIP_TRY(d_edges.alloc(8 * cap));
+    HIP_TRY(d_count.alloc(16));
+    rc = ans_dev_expand(g, d.in.as<uint8_t>(), d.offs.as<uint64_t>(), d.lens.as<uint32_t>(), nchunks,
+                        d_slots.as<uint8_t>(), slot_cap, s);
+    if (rc) return rc;
+    rc = ans_dev_decode_chunks(gt, d_slots.as<uint8_t>(), nullptr, slot_cap, d.lens.as<uint32_t>(), len, chunk_len,
+                               ANS_GEN_ZEROS, d_dense.p, 1, d.status.as<uint32_t>(), s);
     if (rc) return rc;
     rc = ans_dev_dense_to_edges(g, num_nodes, directed, loops, d_dense.as<uint8_t>(), d_edges.as<uint32_t>(), cap,
-                                d_count.as<uint64_t>(), d_status.as<uint32_t>(), s);
+                                d_count.as<uint64_t>(), d.status.as<uint32_t>(), s);
     if (rc) return rc;
     int st = 0;
-    if ((rc = ans_dev_status(g, d_status.as<uint32_t>(), s, &st))) return rc;
+    if ((rc = ans_dev_status(g, d.status.as<uint32_t>(), s, &st))) return rc;
     uint64_t count = 0;
     HIP_TRY(hipMemcpy(&count, d_count.p, 8, hipMemcpyDeviceToHost));
     *num_edges = count;
@@ -663,10 +604,13 @@ int ans_gpu_dense_sets_encode(ans_gpu_table* gt, uint64_t num_graphs, const uint
     const hipStream_t s = gp->stream;
     std::vector<uint64_t> eo(edge_offsets, edge_offsets + num_graphs + 1);
     for (auto& v : eo) v -= edge_offsets[0];
-    Buf d_dense, d_edges, d_nn, d_S, d_eo, d_status;
-    if (!d_dense.alloc(S[num_graphs] + 16) || !d_edges.alloc(8 * m) || !d_nn.alloc(4 * num_graphs) ||
-        !d_S.alloc(8 * (num_graphs + 1)) || !d_eo.alloc(8 * (num_graphs + 1)) || !d_status.alloc(16))
-        return ANS_E_DEVICE;
+    DevBuf d_dense, d_edges, d_nn, d_S, d_eo, d_status;
+    HIP_TRY(d_dense.alloc(S[num_graphs] + 16));
+    HIP_TRY(d_edges.alloc(8 * m));
+    HIP_TRY(d_nn.alloc(4 * num_graphs));
+    HIP_TRY(d_S.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_eo.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_status.alloc(16));
     if (m) HIP_TRY(hipMemcpyAsync(d_edges.p, edges + 2 * edge_offsets[0], 8 * m, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_nn.p, num_nodes, 4 * num_graphs, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_S.p, S.data(), 8 * (num_graphs + 1), hipMemcpyHostToDevice, s));
@@ -681,10 +625,7 @@ int ans_gpu_dense_sets_encode(ans_gpu_table* gt, uint64_t num_graphs, const uint
                                                                   d_status.as<uint32_t>());
         HIP_TRY(hipGetLastError());
     }
-    int st = 0;
-    int rc = ans_dev_status(gp, d_status.as<uint32_t>(), s, &st);
-    if (rc) return rc;
-    if (st) return st;
+    if (const int rc = read_status(gp, d_status.as<uint32_t>(), s)) return rc;
     return ans_encode_var_from_device(gt, d_dense.p, 1, num_graphs, S.data(), out, out_cap, offsets, lens, total);
 } ANS_CATCH
 
@@ -699,46 +640,43 @@ int ans_gpu_dense_sets_decode(ans_gpu_table* gt, uint64_t num_graphs, const uint
     if (num_graphs == 0) return ANS_OK;
     std::vector<uint64_t> S;
     dataset_space(num_graphs, num_nodes, directed, loops, S);
-    std::vector<uint32_t> l32(num_graphs);
-    for (uint64_t g = 0; g < num_graphs; ++g) {
-        if (lens[g] > 0xffffffffull || offsets[g] > in_len || lens[g] > in_len - offsets[g]) return ANS_E_LEN;
-        l32[g] = static_cast<uint32_t>(lens[g]);
-    }
+    std::vector<uint32_t> l32;
+    int rc = narrow_lens(offsets, lens, num_graphs, in_len, l32);
+    if (rc) return rc;
     if (in_len && !in) return ANS_E_ARG;
     const uint64_t len = S[num_graphs];
     ans_gpu* gp = gt->g;
     HIP_TRY(hipSetDevice(gp->device));
     const hipStream_t s = gp->stream;
     const uint64_t ntiles = (len + kTileSlots - 1) / kTileSlots;
-    Buf d_in, d_offs, d_lens, d_S, d_nn, d_dense, d_status, d_edges, d_scan, d_eo;
-    if (!d_in.alloc(in_len + 128) || !d_offs.alloc(8 * num_graphs) || !d_lens.alloc(4 * num_graphs) ||
-        !d_S.alloc(8 * (num_graphs + 1)) || !d_nn.alloc(4 * num_graphs) || !d_dense.alloc(len + 16) ||
-        !d_status.alloc(16) || !d_edges.alloc(8 * cap) || !d_scan.alloc(12 * ntiles + 16) ||
-        !d_eo.alloc(8 * (num_graphs + 1)))
-        return ANS_E_DEVICE;
-    if (in_len) HIP_TRY(hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_offs.p, offsets, 8 * num_graphs, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_lens.p, l32.data(), 4 * num_graphs, hipMemcpyHostToDevice, s));
+    DevStreams d;
+    DevBuf d_S, d_nn, d_dense, d_edges, d_scan, d_eo;
+    if ((rc = upload_streams(in, in_len, offsets, l32, s, d))) return rc;
+    HIP_TRY(d_S.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_nn.alloc(4 * num_graphs));
+    HIP_TRY(d_dense.alloc(len + 16));
+    HIP_TRY(d_edges.alloc(8 * cap));
+    HIP_TRY(d_scan.alloc(12 * ntiles + 16));
+    HIP_TRY(d_eo.alloc(8 * (num_graphs + 1)));
     HIP_TRY(hipMemcpyAsync(d_S.p, S.data(), 8 * (num_graphs + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_nn.p, num_nodes, 4 * num_graphs, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_status.p, 0, 16, s));
     uint64_t maxlen = 0;  // the longest graph's slot count: the staged fast decoder (ans_ctx.hpp)
     for (uint64_t g = 0; g < num_graphs; ++g) maxlen = std::max(maxlen, S[g + 1] - S[g]);
-    int rc = dev_decode_var(gt, d_in.as<uint8_t>(), d_offs.as<uint64_t>(), 0, d_lens.as<uint32_t>(), num_graphs,
-                            d_S.as<uint64_t>(), ANS_GEN_ZEROS, 0, d_dense.p, 1, d_status.as<uint32_t>(), s,
-                            staged_lmax(num_graphs, maxlen, len, 1));
+    rc = dev_decode_var(gt, d.in.as<uint8_t>(), d.offs.as<uint64_t>(), 0, d.lens.as<uint32_t>(), num_graphs,
+                        d_S.as<uint64_t>(), ANS_GEN_ZEROS, 0, d_dense.p, 1, d.status.as<uint32_t>(), s,
+                        staged_lmax(num_graphs, maxlen, len, 1));
     if (rc) return rc;
     auto* base = d_scan.as<uint64_t>();
     auto* counts = reinterpret_cast<uint32_t*>(base + ntiles);
-    uint64_t* d_total = d_status.as<uint64_t>() + 1;  // second 8 bytes of the status block
+    uint64_t* d_total = d.status.as<uint64_t>() + 1;  // second 8 bytes of the status block
     if (ntiles) {
         k_tile_count<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(d_dense.as<uint8_t>(), len, counts);
         HIP_TRY(hipGetLastError());
-        k_tile_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_total);
+        k_excl_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_total);
         HIP_TRY(hipGetLastError());
         k_tile_emit_multi<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(
             directed ? 1u : 0u, loops ? 1u : 0u, d_nn.as<uint32_t>(), d_S.as<uint64_t>(), num_graphs,
-            d_dense.as<uint8_t>(), len, base, d_edges.as<uint32_t>(), cap, d_status.as<uint32_t>());
+            d_dense.as<uint8_t>(), len, base, d_edges.as<uint32_t>(), cap, d.status.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         k_graph_edge_offsets<<<blocks_for(num_graphs + 1, 256), 256, 0, s>>>(d_dense.as<uint8_t>(), d_S.as<uint64_t>(),
                                                                            num_graphs, base, d_total,
@@ -746,7 +684,7 @@ int ans_gpu_dense_sets_decode(ans_gpu_table* gt, uint64_t num_graphs, const uint
         HIP_TRY(hipGetLastError());
     }
     int st = 0;
-    if ((rc = ans_dev_status(gp, d_status.as<uint32_t>(), s, &st))) return rc;
+    if ((rc = ans_dev_status(gp, d.status.as<uint32_t>(), s, &st))) return rc;
     if (st && st != ANS_E_LEN) return st;
     if (ntiles) HIP_TRY(hipMemcpy(edge_offsets, d_eo.p, 8 * (num_graphs + 1), hipMemcpyDeviceToHost));
     else std::fill(edge_offsets, edge_offsets + num_graphs + 1, 0);
@@ -758,7 +696,6 @@ int ans_gpu_dense_sets_decode(ans_gpu_table* gt, uint64_t num_graphs, const uint
 
 // ---- GraphIID<NodeC, EdgeC, ErdosRenyi> over a dataset, one message per graph (include/ans_capi.h
 // section 5b; src/graph_codec.rs:19-94, the --er models of src/benchmark.rs:308-358)
-static bool graph_kind_ok(int k) { return k == ANS_GEN_ZEROS || k == ANS_GEN_EMPTY || k == ANS_GEN_RANDOM; }
 
 // node-label and slot offsets of every graph; ANS_E_ARG for a node count of 2^32 or more
 static int graph_offsets(uint64_t num_graphs, const uint32_t* num_nodes, int directed, int loops,
@@ -774,7 +711,7 @@ int ans_gpu_graphs_encode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
                           const uint64_t* edge_offsets, int gen_kind, uint64_t seed, uint8_t* out, uint64_t out_cap,
                           uint64_t* offsets, uint64_t* lens, uint64_t* total) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!ts || !total || !graph_kind_ok(gen_kind) || (num_graphs && (!num_nodes || !edge_offsets))) return ANS_E_ARG;
+    if (!ts || !total || !valid_kind(gen_kind) || (num_graphs && (!num_nodes || !edge_offsets))) return ANS_E_ARG;
     *total = 0;
     if (num_graphs == 0) return ANS_OK;
     if (out && (!offsets || !lens)) return ANS_E_ARG;
@@ -796,15 +733,23 @@ int ans_gpu_graphs_encode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
     ans_gpu* gp = ans_tableset_gpu(ts);
     HIP_TRY(hipSetDevice(gp->device));
     const hipStream_t s = gp->stream;
-    Buf d_nn, d_NO, d_S, d_eo, d_nl, d_edges, d_el, d_dense, d_rdense, d_rid, d_sorted, d_scan, d_status, d_slots,
-        d_lens, d_offs, d_out;
-    if (!d_nn.alloc(4 * num_graphs) || !d_NO.alloc(8 * (num_graphs + 1)) || !d_S.alloc(8 * (num_graphs + 1)) ||
-        !d_eo.alloc(8 * (num_graphs + 1)) || !d_nl.alloc(nl ? 4 * NO[num_graphs] : 0) || !d_edges.alloc(8 * m) ||
-        !d_el.alloc(el ? 4 * m : 0) || !d_dense.alloc(len + 16) || !d_rdense.alloc(el ? len + 16 : 0) ||
-        !d_rid.alloc(el ? 4 * len : 0) || !d_sorted.alloc(el ? 4 * m : 0) || !d_scan.alloc(12 * ntiles + 16) ||
-        !d_status.alloc(16) || !d_slots.alloc(num_graphs * slot_cap) || !d_lens.alloc(4 * num_graphs) ||
-        !d_offs.alloc(8 * num_graphs))
-        return ANS_E_DEVICE;
+    DevBuf d_nn, d_NO, d_S, d_eo, d_nl, d_edges, d_el, d_dense, d_rdense, d_rid, d_sorted, d_scan, d_status, d_slots,
+        d_lens;
+    HIP_TRY(d_nn.alloc(4 * num_graphs));
+    HIP_TRY(d_NO.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_S.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_eo.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_nl.alloc(nl ? 4 * NO[num_graphs] : 0));
+    HIP_TRY(d_edges.alloc(8 * m));
+    HIP_TRY(d_el.alloc(el ? 4 * m : 0));
+    HIP_TRY(d_dense.alloc(len + 16));
+    HIP_TRY(d_rdense.alloc(el ? len + 16 : 0));
+    HIP_TRY(d_rid.alloc(el ? 4 * len : 0));
+    HIP_TRY(d_sorted.alloc(el ? 4 * m : 0));
+    HIP_TRY(d_scan.alloc(12 * ntiles + 16));
+    HIP_TRY(d_status.alloc(16));
+    HIP_TRY(d_slots.alloc(num_graphs * slot_cap));
+    HIP_TRY(d_lens.alloc(4 * num_graphs));
     HIP_TRY(hipMemcpyAsync(d_nn.p, num_nodes, 4 * num_graphs, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_NO.p, NO.data(), 8 * (num_graphs + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_S.p, S.data(), 8 * (num_graphs + 1), hipMemcpyHostToDevice, s));
@@ -834,48 +779,23 @@ int ans_gpu_graphs_encode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
             auto* counts = reinterpret_cast<uint32_t*>(base + ntiles);
             k_tile_count<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(d_rdense.as<uint8_t>(), len, counts);
             HIP_TRY(hipGetLastError());
-            k_tile_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_status.as<uint64_t>() + 1);
+            k_excl_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_status.as<uint64_t>() + 1);
             HIP_TRY(hipGetLastError());
             k_graph_sort_labels<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(
                 d_rdense.as<uint8_t>(), len, base, d_rid.as<uint32_t>(), d_el.as<uint32_t>(), m, d_sorted.as<uint32_t>());
             HIP_TRY(hipGetLastError());
         }
     }
-    int st = 0;
-    int rc = ans_dev_status(gp, d_status.as<uint32_t>(), s, &st);
+    int rc = read_status(gp, d_status.as<uint32_t>(), s);
     if (rc) return rc;
-    if (st) return st;
     const GraphLayout gl{d_NO.as<uint64_t>(), d_S.as<uint64_t>(), d_eo.as<uint64_t>(), nl ? node_table : kNoTable,
                          el ? edge_table : kNoTable, edge_indicator_table};
     rc = ans_tableset_graph_encode(ts, gl, num_graphs, d_nl.as<uint32_t>(), d_dense.as<uint8_t>(),
                                    d_sorted.as<uint32_t>(), gen_kind, seed, d_slots.as<uint8_t>(), slot_cap,
                                    d_lens.as<uint32_t>(), d_status.as<uint32_t>(), s);
-    if (rc) return rc;
-    if ((rc = ans_dev_status(gp, d_status.as<uint32_t>(), s, &st))) return rc;
-    if (st) return st;
-    std::vector<uint32_t> hl(num_graphs);
-    HIP_TRY(hipMemcpy(hl.data(), d_lens.p, 4 * num_graphs, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> off(num_graphs);
-    uint64_t acc = 0;
-    for (uint64_t g = 0; g < num_graphs; ++g) {
-        off[g] = acc;
-        acc += hl[g];
-    }
-    *total = acc;
-    if (!out) return ANS_OK;
-    if (out_cap < acc) return ANS_E_LEN;
-    for (uint64_t g = 0; g < num_graphs; ++g) {
-        offsets[g] = off[g];
-        lens[g] = hl[g];
-    }
-    if (!d_out.alloc(acc + 16)) return ANS_E_DEVICE;
-    HIP_TRY(hipMemcpyAsync(d_offs.p, off.data(), 8 * num_graphs, hipMemcpyHostToDevice, s));
-    if ((rc = ans_dev_compact(gp, d_slots.as<uint8_t>(), slot_cap, d_lens.as<uint32_t>(), d_offs.as<uint64_t>(),
-                              num_graphs, d_out.as<uint8_t>(), s)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, acc, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ANS_OK;
+    if (rc || (rc = read_status(gp, d_status.as<uint32_t>(), s))) return rc;
+    return download_container(gp, d_slots.as<uint8_t>(), slot_cap, d_lens.as<uint32_t>(), num_graphs, s, out, out_cap,
+                              offsets, lens, total);
 } ANS_CATCH
 
 int ans_gpu_graphs_decode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t edge_table, uint32_t edge_indicator_table,
@@ -884,18 +804,16 @@ int ans_gpu_graphs_decode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
                           uint32_t* node_labels, uint32_t* edges, uint32_t* edge_labels, uint64_t cap,
                           uint64_t* edge_offsets) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!ts || !edge_offsets || !graph_kind_ok(gen_kind) || (num_graphs && (!num_nodes || !offsets || !lens)))
+    if (!ts || !edge_offsets || !valid_kind(gen_kind) || (num_graphs && (!num_nodes || !offsets || !lens)))
         return ANS_E_ARG;
     const bool nl = node_table != ANS_NO_TABLE, el = edge_table != ANS_NO_TABLE;
     if (cap && (!edges || (el && !edge_labels))) return ANS_E_ARG;
     edge_offsets[0] = 0;
     if (num_graphs == 0) return ANS_OK;
     if (in_len && !in) return ANS_E_ARG;
-    std::vector<uint32_t> l32(num_graphs);
-    for (uint64_t g = 0; g < num_graphs; ++g) {
-        if (lens[g] > 0xffffffffull || offsets[g] > in_len || lens[g] > in_len - offsets[g]) return ANS_E_LEN;
-        l32[g] = static_cast<uint32_t>(lens[g]);
-    }
+    std::vector<uint32_t> l32;
+    int rc = narrow_lens(offsets, lens, num_graphs, in_len, l32);
+    if (rc) return rc;
     std::vector<uint64_t> NO, S;
     graph_offsets(num_graphs, num_nodes, directed, loops, NO, S);
     if (nl && NO[num_graphs] && !node_labels) return ANS_E_ARG;
@@ -903,30 +821,32 @@ int ans_gpu_graphs_decode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
     ans_gpu* gp = ans_tableset_gpu(ts);
     HIP_TRY(hipSetDevice(gp->device));
     const hipStream_t s = gp->stream;
-    Buf d_in, d_offs, d_lens, d_nn, d_NO, d_S, d_nl, d_dense, d_rdense, d_escr, d_ecnt, d_scan, d_status, d_eo,
-        d_edges, d_el;
-    if (!d_in.alloc(in_len + 16) || !d_offs.alloc(8 * num_graphs) || !d_lens.alloc(4 * num_graphs) ||
-        !d_nn.alloc(4 * num_graphs) || !d_NO.alloc(8 * (num_graphs + 1)) || !d_S.alloc(8 * (num_graphs + 1)) ||
-        !d_nl.alloc(nl ? 4 * NO[num_graphs] : 0) || !d_dense.alloc(len + 16) || !d_rdense.alloc(len + 16) ||
-        !d_escr.alloc(el ? 4 * len : 0) || !d_ecnt.alloc(8 * num_graphs) || !d_scan.alloc(12 * ntiles + 16) ||
-        !d_status.alloc(16) || !d_eo.alloc(8 * (num_graphs + 1)) || !d_edges.alloc(8 * cap) ||
-        !d_el.alloc(el ? 4 * cap : 0))
-        return ANS_E_DEVICE;
-    if (in_len) HIP_TRY(hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_offs.p, offsets, 8 * num_graphs, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_lens.p, l32.data(), 4 * num_graphs, hipMemcpyHostToDevice, s));
+    DevStreams d;
+    DevBuf d_nn, d_NO, d_S, d_nl, d_dense, d_rdense, d_escr, d_ecnt, d_scan, d_eo, d_edges, d_el;
+    if ((rc = upload_streams(in, in_len, offsets, l32, s, d))) return rc;
+    HIP_TRY(d_nn.alloc(4 * num_graphs));
+    HIP_TRY(d_NO.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_S.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_nl.alloc(nl ? 4 * NO[num_graphs] : 0));
+    HIP_TRY(d_dense.alloc(len + 16));
+    HIP_TRY(d_rdense.alloc(len + 16));
+    HIP_TRY(d_escr.alloc(el ? 4 * len : 0));
+    HIP_TRY(d_ecnt.alloc(8 * num_graphs));
+    HIP_TRY(d_scan.alloc(12 * ntiles + 16));
+    HIP_TRY(d_eo.alloc(8 * (num_graphs + 1)));
+    HIP_TRY(d_edges.alloc(8 * cap));
+    HIP_TRY(d_el.alloc(el ? 4 * cap : 0));
     HIP_TRY(hipMemcpyAsync(d_nn.p, num_nodes, 4 * num_graphs, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_NO.p, NO.data(), 8 * (num_graphs + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_S.p, S.data(), 8 * (num_graphs + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_status.p, 0, 16, s));
     if (len) HIP_TRY(hipMemsetAsync(d_rdense.p, 0, len, s));
     const GraphLayout gl{d_NO.as<uint64_t>(), d_S.as<uint64_t>(), nullptr, nl ? node_table : kNoTable,
                          el ? edge_table : kNoTable, edge_indicator_table};
-    int rc = ans_tableset_graph_decode(ts, gl, num_graphs, d_in.as<uint8_t>(), d_offs.as<uint64_t>(),
-                                       d_lens.as<uint32_t>(), gen_kind, seed, d_nl.as<uint32_t>(), d_dense.as<uint8_t>(),
-                                       d_escr.as<uint32_t>(), d_ecnt.as<uint64_t>(), d_status.as<uint32_t>(), s);
+    rc = ans_tableset_graph_decode(ts, gl, num_graphs, d.in.as<uint8_t>(), d.offs.as<uint64_t>(), d.lens.as<uint32_t>(),
+                                   gen_kind, seed, d_nl.as<uint32_t>(), d_dense.as<uint8_t>(), d_escr.as<uint32_t>(),
+                                   d_ecnt.as<uint64_t>(), d.status.as<uint32_t>(), s);
     if (rc) return rc;
-    uint64_t* d_total = d_status.as<uint64_t>() + 1;
+    uint64_t* d_total = d.status.as<uint64_t>() + 1;
     if (ntiles) {  // EdgesIID::pop: the edges sorted by index (row-major rank), labels beside them
         auto* base = d_scan.as<uint64_t>();
         auto* counts = reinterpret_cast<uint32_t*>(base + ntiles);
@@ -936,7 +856,7 @@ int ans_gpu_graphs_decode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
         HIP_TRY(hipGetLastError());
         k_tile_count<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(d_rdense.as<uint8_t>(), len, counts);
         HIP_TRY(hipGetLastError());
-        k_tile_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_total);
+        k_excl_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_total);
         HIP_TRY(hipGetLastError());
         k_graph_edge_offsets<<<blocks_for(num_graphs + 1, 256), 256, 0, s>>>(
             d_rdense.as<uint8_t>(), d_S.as<uint64_t>(), num_graphs, base, d_total, d_eo.as<uint64_t>());
@@ -944,11 +864,11 @@ int ans_gpu_graphs_decode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
         k_graph_emit_rows<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(
             directed ? 1u : 0u, loops ? 1u : 0u, d_nn.as<uint32_t>(), d_S.as<uint64_t>(), num_graphs,
             d_rdense.as<uint8_t>(), len, base, d_eo.as<uint64_t>(), d_escr.as<uint32_t>(), d_edges.as<uint32_t>(),
-            el ? d_el.as<uint32_t>() : nullptr, cap, d_status.as<uint32_t>());
+            el ? d_el.as<uint32_t>() : nullptr, cap, d.status.as<uint32_t>());
         HIP_TRY(hipGetLastError());
     }
     int st = 0;
-    if ((rc = ans_dev_status(gp, d_status.as<uint32_t>(), s, &st))) return rc;
+    if ((rc = ans_dev_status(gp, d.status.as<uint32_t>(), s, &st))) return rc;
     if (st && st != ANS_E_LEN) return st;
     if (ntiles) HIP_TRY(hipMemcpy(edge_offsets, d_eo.p, 8 * (num_graphs + 1), hipMemcpyDeviceToHost));
     else std::fill(edge_offsets, edge_offsets + num_graphs + 1, 0);

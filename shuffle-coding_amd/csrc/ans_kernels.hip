@@ -19,8 +19,10 @@
 #include <cstring>
 #include <vector>
 
+#include "ans_hostio.hpp"
 #include "ans_kcommon.hpp"
 #include "ans_launch.hpp"
+#include "ans_scan.hpp"
 
 using namespace shuffle_coding::launch;
 
@@ -241,22 +243,6 @@ __global__ __launch_bounds__(kBlock) void k_compact_dense(const uint8_t* __restr
     if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) wave_pack(out + off, src, len, lane);
     else wave_copy(out + off, src, len, lane);
 }
-
-bool valid_width(int w) { return w == 1 || w == 2 || w == 4; }
-bool valid_kind(int k) { return k == ANS_GEN_ZEROS || k == ANS_GEN_EMPTY || k == ANS_GEN_RANDOM; }
-
-int lowest_status(uint32_t bits) {
-    for (int k = 1; k < 32; ++k)
-        if (bits & (1u << k)) return k;
-    return ANS_OK;
-}
-
-// Device buffer that frees itself (host API convenience only; never in a timed path).
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
 
 // 1/d rounded UP (fma(r, d, -1) is the exact sign of r d - 1): kNormSmall's exact high division
 // step (ans_fast.hpp div_hi) needs r >= 1/d, and r - 1/d < 2^-52 / d keeps its estimates as
@@ -638,32 +624,6 @@ int build_fast_table(ans_gpu_table* gt, const Categorical& cat) {
 
 constexpr int kPipeScattered = -1;
 
-// Exclusive scan of a batch's stream lengths: offs[j] = sum of lens[0..j), offs[n] = total.
-// One workgroup (n <= a few 10^5 per batch): each thread sums a contiguous segment, the
-// segment sums are scanned in LDS, then each thread writes its segment's offsets.
-__global__ __launch_bounds__(1024) void k_scan_lens(const uint32_t* __restrict__ lens, uint64_t n,
-                                                    uint64_t* __restrict__ offs) {
-    __shared__ uint64_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint64_t per = (n + 1023) / 1024, b = t * per, e = b + per < n ? b + per : n;
-    uint64_t sum = 0;
-    for (uint64_t i = b; i < e; ++i) sum += lens[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint64_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - sum;
-    for (uint64_t i = b; i < e; ++i) {
-        offs[i] = run;
-        run += lens[i];
-    }
-    if (t == 1023) offs[n] = part[1023];
-}
-
 // the workspace slots in use
 struct SlotRange {
     PipeSlot* a;
@@ -838,7 +798,8 @@ int pipe_encode(ans_gpu_table* gt, const void* syms, uint64_t n, uint64_t chunk_
         int r = launch_encode<Sym>(gt, s.d_syms, nb, chunk_len, s.d_slots, slot_cap, s.d_lens, p->d_status, sc,
                                    fast::ChunkInit{ini.kind, ini.seed + c0});
         if (r) return r;
-        k_scan_lens<<<1, 1024, 0, sc>>>(s.d_lens, nc, s.d_offs);
+        // the batch's stream offsets: offs[j] = sum of lens[0..j), offs[nc] = total (ans_scan.hpp)
+        k_excl_scan<<<1, 1024, 0, sc>>>(s.d_lens, nc, s.d_offs, s.d_offs + nc);
         HIP_TRY(hipGetLastError());
         if (copy) {
             k_compact<<<grid_for(nc * 64), kBlock, 0, sc>>>(s.d_slots, slot_cap, s.d_lens, s.d_offs, nc, s.d_dense);
@@ -880,9 +841,7 @@ int pipe_encode(ans_gpu_table* gt, const void* syms, uint64_t n, uint64_t chunk_
     if (nbatch && (rc = finish(nbatch - 1))) return rc;
     HIP_TRY(hipStreamSynchronize(p->s_out));
     HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    int st = 0;
-    if ((rc = ans_dev_status(gt->g, p->d_status, gt->g->stream, &st))) return rc;
-    if (st) return st;
+    if ((rc = read_status(gt->g, p->d_status, gt->g->stream))) return rc;
     *total = acc;
     return len_err;
 }
@@ -948,9 +907,7 @@ int pipe_decode(ans_gpu_table* gt, const uint8_t* in, const uint64_t* offsets, c
     }
     HIP_TRY(hipStreamSynchronize(p->s_out));
     HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    int st = 0;
-    if ((rc = ans_dev_status(gt->g, p->d_status, gt->g->stream, &st))) return rc;
-    return st;
+    return read_status(gt->g, p->d_status, gt->g->stream);
 }
 
 // ---- page-locked host buffers: the GPU moves the bytes itself (no runtime copy calls)
@@ -1005,36 +962,20 @@ __global__ __launch_bounds__(256) void k_xfer(uint8_t* __restrict__ dst, const u
     xfer_bytes(dst, src, bytes);
 }
 
-// Batch scan for the mapped encoder: like k_scan_lens, plus the running container offset.
-// base = *acc (the bytes of all earlier batches), *acc += total; offs[n] = total,
-// offs[n+1] = base; each chunk's absolute offset and length go to the host arrays.
+// Batch scan for the mapped encoder: the batch's offsets (ans_scan.hpp) plus the running
+// container offset.  base = *acc (the bytes of all earlier batches), *acc += total; offs[n] =
+// total, offs[n+1] = base; each chunk's absolute offset and length go to the host arrays.
 __global__ __launch_bounds__(1024) void k_scan_carry(const uint32_t* __restrict__ lens, uint64_t n,
                                                      uint64_t* __restrict__ offs, uint64_t* __restrict__ acc,
                                                      uint64_t* __restrict__ h_offs, uint64_t* __restrict__ h_lens) {
-    __shared__ uint64_t part[1024];
     __shared__ uint64_t base;
     const uint32_t t = threadIdx.x;
     if (t == 0) base = *acc;
-    const uint64_t per = (n + 1023) / 1024, b = t * per, e = b + per < n ? b + per : n;
-    uint64_t sum = 0;
-    for (uint64_t i = b; i < e; ++i) sum += lens[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        const uint64_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - sum;
-    for (uint64_t i = b; i < e; ++i) {
-        offs[i] = run;
-        run += lens[i];
-    }
+    const uint64_t total = block_excl_scan(lens, n, offs);  // (its barriers publish base)
     if (t == 1023) {
-        offs[n] = part[1023];
+        offs[n] = total;
         offs[n + 1] = base;
-        *acc = base + part[1023];
+        *acc = base + total;
     }
     __syncthreads();
     for (uint64_t i = t; i < n; i += 1024) {  // coalesced writes across PCIe
@@ -1236,9 +1177,7 @@ int pipe_decode_mapped(ans_gpu_table* gt, const uint8_t* in_dev, const uint64_t*
     }
     HIP_TRY(hipStreamSynchronize(p->s_out));
     HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    int st = 0;
-    if ((rc = ans_dev_status(gt->g, p->d_status, s0, &st))) return rc;
-    return st;
+    return read_status(gt->g, p->d_status, s0);
 }
 
 }  // namespace
@@ -1257,46 +1196,19 @@ int ans_encode_var_from_device(ans_gpu_table* gt, const void* d_syms, int sym_by
     ans_gpu_slot_capacity(gt, maxlen, &slot_cap);
     HIP_TRY(hipSetDevice(gt->g->device));
     const hipStream_t s = gt->g->stream;
-    DevBuf d_starts, d_slots, d_lens, d_status, d_offs, d_out;
+    DevBuf d_starts, d_slots, d_lens, d_status;
     HIP_TRY(d_starts.alloc(8 * (nchunks + 1)));
     HIP_TRY(d_slots.alloc(nchunks * slot_cap));
     HIP_TRY(d_lens.alloc(4 * nchunks));
     HIP_TRY(d_status.alloc(4));
     HIP_TRY(hipMemcpyAsync(d_starts.p, starts, 8 * (nchunks + 1), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(d_status.p, 0, 4, s));
-    int rc = dev_encode_var(gt, d_syms, sym_bytes, nchunks, static_cast<uint64_t*>(d_starts.p), gen_kind, seed,
-                            static_cast<uint8_t*>(d_slots.p), slot_cap, static_cast<uint32_t*>(d_lens.p),
-                            static_cast<uint32_t*>(d_status.p), s,
+    int rc = dev_encode_var(gt, d_syms, sym_bytes, nchunks, d_starts.as<uint64_t>(), gen_kind, seed,
+                            d_slots.as<uint8_t>(), slot_cap, d_lens.as<uint32_t>(), d_status.as<uint32_t>(), s,
                             staged_lmax(nchunks, maxlen, starts[nchunks] - starts[0], sym_bytes));
-    if (rc) return rc;
-    int st = 0;
-    if ((rc = ans_dev_status(gt->g, static_cast<uint32_t*>(d_status.p), s, &st))) return rc;
-    if (st) return st;
-    std::vector<uint32_t> hl(nchunks);
-    HIP_TRY(hipMemcpy(hl.data(), d_lens.p, 4 * nchunks, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> off(nchunks);
-    uint64_t acc = 0;
-    for (uint64_t c = 0; c < nchunks; ++c) {
-        off[c] = acc;
-        acc += hl[c];
-    }
-    *total = acc;
-    if (!out) return ANS_OK;
-    if (out_cap < acc) return ANS_E_LEN;
-    for (uint64_t c = 0; c < nchunks; ++c) {
-        offsets[c] = off[c];
-        lens[c] = hl[c];
-    }
-    if (!acc) return ANS_OK;
-    HIP_TRY(d_offs.alloc(8 * nchunks));
-    HIP_TRY(d_out.alloc(acc));
-    HIP_TRY(hipMemcpyAsync(d_offs.p, off.data(), 8 * nchunks, hipMemcpyHostToDevice, s));
-    if ((rc = ans_dev_compact(gt->g, static_cast<uint8_t*>(d_slots.p), slot_cap, static_cast<uint32_t*>(d_lens.p),
-                              static_cast<uint64_t*>(d_offs.p), nchunks, static_cast<uint8_t*>(d_out.p), s)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, acc, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ANS_OK;
+    if (rc || (rc = read_status(gt->g, d_status.as<uint32_t>(), s))) return rc;
+    return download_container(gt->g, d_slots.as<uint8_t>(), slot_cap, d_lens.as<uint32_t>(), nchunks, s, out, out_cap,
+                              offsets, lens, total);
 }
 
 // ====================================================================== C ABI (GPU part)
@@ -1476,7 +1388,7 @@ int ans_dev_encode_chunks_ex(ans_gpu_table* gt, const void* d_syms, int sym_byte
                              int gen_kind, uint64_t seed, uint8_t* d_slots, uint64_t slot_cap, uint32_t* d_lens,
                              uint32_t* d_status, void* stream) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !d_status || !valid_width(sym_bytes) || chunk_len == 0 || (slot_cap & 15) || !valid_kind(gen_kind))
+    if (!gt || !d_status || !valid_width_u32(sym_bytes) || chunk_len == 0 || (slot_cap & 15) || !valid_kind(gen_kind))
         return ANS_E_ARG;
     if (n && (!d_syms || !d_slots || !d_lens)) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
@@ -1485,11 +1397,9 @@ int ans_dev_encode_chunks_ex(ans_gpu_table* gt, const void* d_syms, int sym_byte
         return ans_tableset_dev_encode(gt->ts64, d_syms, sym_bytes, nullptr, n, chunk_len, (n + chunk_len - 1) / chunk_len,
                                        d_slots, slot_cap, d_lens, d_status, gen_kind, seed, s);
     const fast::ChunkInit ini{gen_kind, seed};
-    switch (sym_bytes) {
-    case 1: return launch_encode<uint8_t>(gt, d_syms, n, chunk_len, d_slots, slot_cap, d_lens, d_status, s, ini);
-    case 2: return launch_encode<uint16_t>(gt, d_syms, n, chunk_len, d_slots, slot_cap, d_lens, d_status, s, ini);
-    default: return launch_encode<uint32_t>(gt, d_syms, n, chunk_len, d_slots, slot_cap, d_lens, d_status, s, ini);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return launch_encode<decltype(t)>(gt, d_syms, n, chunk_len, d_slots, slot_cap, d_lens, d_status, s, ini);
+    });
 } ANS_CATCH
 
 int ans_dev_encode_chunks(ans_gpu_table* gt, const void* d_syms, int sym_bytes, uint64_t n, uint64_t chunk_len,
@@ -1502,7 +1412,7 @@ int ans_dev_decode_chunks_ex(ans_gpu_table* gt, const uint8_t* d_in, const uint6
                              const uint32_t* d_lens, uint64_t n, uint64_t chunk_len, int gen_kind, uint64_t seed,
                              void* d_syms, int sym_bytes, uint32_t* d_status, void* stream) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !d_status || !valid_width(sym_bytes) || chunk_len == 0 || !valid_kind(gen_kind)) return ANS_E_ARG;
+    if (!gt || !d_status || !valid_width_u32(sym_bytes) || chunk_len == 0 || !valid_kind(gen_kind)) return ANS_E_ARG;
     if (n && (!d_in || !d_lens || !d_syms)) return ANS_E_ARG;
     if (sym_bytes == 1 && gt->t.nsym > 256) return ANS_E_ARG;
     if (sym_bytes == 2 && gt->t.nsym > 65536) return ANS_E_ARG;
@@ -1512,11 +1422,10 @@ int ans_dev_decode_chunks_ex(ans_gpu_table* gt, const uint8_t* d_in, const uint6
         return ans_tableset_dev_decode(gt->ts64, d_in, d_offsets, slot_cap, d_lens, nullptr, n, chunk_len,
                                        (n + chunk_len - 1) / chunk_len, gen_kind, seed, d_syms, sym_bytes, d_status, s);
     const fast::ChunkInit ini{gen_kind, seed};
-    switch (sym_bytes) {
-    case 1: return launch_decode<uint8_t>(gt, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, gen_kind, d_syms, d_status, s, ini);
-    case 2: return launch_decode<uint16_t>(gt, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, gen_kind, d_syms, d_status, s, ini);
-    default: return launch_decode<uint32_t>(gt, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, gen_kind, d_syms, d_status, s, ini);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return launch_decode<decltype(t)>(gt, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, gen_kind, d_syms, d_status,
+                                          s, ini);
+    });
 } ANS_CATCH
 
 int ans_dev_decode_chunks(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_offsets, uint64_t slot_cap,
@@ -1530,16 +1439,14 @@ int ans_dev_decode_chunks(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t
 int ans_dev_gen_iid(ans_gpu_table* gt, uint64_t seed, uint64_t start, uint64_t n, void* d_syms, int sym_bytes,
                     void* stream) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || (n && !d_syms)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes) || (n && !d_syms)) return ANS_E_ARG;
     if (gt->ts64) return ANS_E_NORM_RANGE;  // the synthetic generator reads u32 tables
     if (sym_bytes == 1 && gt->t.nsym > 256) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
     const hipStream_t s = pick(gt, stream);
-    switch (sym_bytes) {
-    case 1: return launch_gen<uint8_t>(gt, seed, start, n, d_syms, s);
-    case 2: return launch_gen<uint16_t>(gt, seed, start, n, d_syms, s);
-    default: return launch_gen<uint32_t>(gt, seed, start, n, d_syms, s);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return launch_gen<decltype(t)>(gt, seed, start, n, d_syms, s);
+    });
 } ANS_CATCH
 
 int ans_dev_check_renorm(ans_gpu* g, const uint64_t* d_heads, const uint32_t* d_windows, uint64_t L, uint64_t n,
@@ -1557,22 +1464,20 @@ int ans_dev_check_renorm(ans_gpu* g, const uint64_t* d_heads, const uint32_t* d_
 int ans_dev_sample_iid(ans_gpu_table* gt, uint64_t seed, uint64_t n, uint64_t chunk_len, void* d_syms, int sym_bytes,
                        void* stream) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || chunk_len == 0 || (n && !d_syms)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes) || chunk_len == 0 || (n && !d_syms)) return ANS_E_ARG;
     if (gt->ts64) return ANS_E_NORM_RANGE;  // the sampler reads u32 tables
     if (sym_bytes == 1 && gt->t.nsym > 256) return ANS_E_ARG;
     if (sym_bytes == 2 && gt->t.nsym > 65536) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
     const hipStream_t s = pick(gt, stream);
-    switch (sym_bytes) {
-    case 1: return launch_sample<uint8_t>(gt, seed, n, chunk_len, d_syms, s);
-    case 2: return launch_sample<uint16_t>(gt, seed, n, chunk_len, d_syms, s);
-    default: return launch_sample<uint32_t>(gt, seed, n, chunk_len, d_syms, s);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return launch_sample<decltype(t)>(gt, seed, n, chunk_len, d_syms, s);
+    });
 } ANS_CATCH
 
 int ans_gpu_sample_iid(ans_gpu_table* gt, uint64_t seed, uint64_t n, uint64_t chunk_len, void* out, int sym_bytes) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || chunk_len == 0 || (n && !out)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes) || chunk_len == 0 || (n && !out)) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
     DevBuf d;
     HIP_TRY(d.alloc(n * sym_bytes));
@@ -1632,7 +1537,7 @@ int dev_encode_var(ans_gpu_table* gt, const void* d_syms, int sym_bytes, uint64_
                           const uint64_t* d_starts, int gen_kind, uint64_t seed, uint8_t* d_slots, uint64_t slot_cap,
                           uint32_t* d_lens, uint32_t* d_status, void* stream, uint64_t lmax) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !d_status || !valid_width(sym_bytes) || (slot_cap & 15) || !valid_kind(gen_kind)) return ANS_E_ARG;
+    if (!gt || !d_status || !valid_width_u32(sym_bytes) || (slot_cap & 15) || !valid_kind(gen_kind)) return ANS_E_ARG;
     if (nchunks && (!d_syms || !d_starts || !d_slots || !d_lens)) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
     const hipStream_t s = pick(gt, stream);
@@ -1640,18 +1545,17 @@ int dev_encode_var(ans_gpu_table* gt, const void* d_syms, int sym_bytes, uint64_
         return ans_tableset_dev_encode(gt->ts64, d_syms, sym_bytes, d_starts, 0, 0, nchunks, d_slots, slot_cap, d_lens,
                                        d_status, gen_kind, seed, s);
     const fast::ChunkInit ini{gen_kind, seed};
-    switch (sym_bytes) {
-    case 1: return launch_encode_var<uint8_t>(gt, d_syms, nchunks, d_starts, d_slots, slot_cap, d_lens, d_status, s, ini, lmax);
-    case 2: return launch_encode_var<uint16_t>(gt, d_syms, nchunks, d_starts, d_slots, slot_cap, d_lens, d_status, s, ini, lmax);
-    default: return launch_encode_var<uint32_t>(gt, d_syms, nchunks, d_starts, d_slots, slot_cap, d_lens, d_status, s, ini, lmax);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return launch_encode_var<decltype(t)>(gt, d_syms, nchunks, d_starts, d_slots, slot_cap, d_lens, d_status, s, ini,
+                                              lmax);
+    });
 } ANS_CATCH
 
 int ans_dev_encode_var_chunks_ex(ans_gpu_table* gt, const void* d_syms, int sym_bytes, uint64_t nchunks,
                                  const uint64_t* d_starts, int gen_kind, uint64_t seed, uint8_t* d_slots,
                                  uint64_t slot_cap, uint32_t* d_lens, uint32_t* d_status, void* stream) try {
     (void)hipGetLastError();
-    if (!gt || !valid_width(sym_bytes)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes)) return ANS_E_ARG;
     if (nchunks && !d_starts) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
     uint64_t lmax = 0;
@@ -1674,7 +1578,7 @@ int dev_decode_var(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_off
                           const uint32_t* d_lens, uint64_t nchunks, const uint64_t* d_starts, int gen_kind,
                           uint64_t seed, void* d_syms, int sym_bytes, uint32_t* d_status, void* stream, uint64_t lmax) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !d_status || !valid_width(sym_bytes) || !valid_kind(gen_kind)) return ANS_E_ARG;
+    if (!gt || !d_status || !valid_width_u32(sym_bytes) || !valid_kind(gen_kind)) return ANS_E_ARG;
     if (nchunks && (!d_in || !d_lens || !d_starts || !d_syms)) return ANS_E_ARG;
     if ((sym_bytes == 1 && gt->t.nsym > 256) || (sym_bytes == 2 && gt->t.nsym > 65536)) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
@@ -1683,18 +1587,17 @@ int dev_decode_var(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_off
         return ans_tableset_dev_decode(gt->ts64, d_in, d_offsets, slot_cap, d_lens, d_starts, 0, 0, nchunks, gen_kind,
                                        seed, d_syms, sym_bytes, d_status, s);
     const fast::ChunkInit ini{gen_kind, seed};
-    switch (sym_bytes) {
-    case 1: return launch_decode_var<uint8_t>(gt, d_in, d_offsets, slot_cap, d_lens, nchunks, d_starts, gen_kind, d_syms, d_status, s, ini, lmax);
-    case 2: return launch_decode_var<uint16_t>(gt, d_in, d_offsets, slot_cap, d_lens, nchunks, d_starts, gen_kind, d_syms, d_status, s, ini, lmax);
-    default: return launch_decode_var<uint32_t>(gt, d_in, d_offsets, slot_cap, d_lens, nchunks, d_starts, gen_kind, d_syms, d_status, s, ini, lmax);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return launch_decode_var<decltype(t)>(gt, d_in, d_offsets, slot_cap, d_lens, nchunks, d_starts, gen_kind, d_syms,
+                                              d_status, s, ini, lmax);
+    });
 } ANS_CATCH
 
 int ans_dev_decode_var_chunks_ex(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_offsets, uint64_t slot_cap,
                                  const uint32_t* d_lens, uint64_t nchunks, const uint64_t* d_starts, int gen_kind,
                                  uint64_t seed, void* d_syms, int sym_bytes, uint32_t* d_status, void* stream) try {
     (void)hipGetLastError();
-    if (!gt || !valid_width(sym_bytes)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes)) return ANS_E_ARG;
     if (nchunks && !d_starts) return ANS_E_ARG;
     HIP_TRY(hipSetDevice(gt->g->device));
     uint64_t lmax = 0;
@@ -1718,7 +1621,7 @@ int ans_gpu_encode_var_chunks_ex(ans_gpu_table* gt, const void* syms, int sym_by
                                  const uint64_t* starts, int gen_kind, uint64_t seed, uint8_t* out, uint64_t out_cap,
                                  uint64_t* offsets, uint64_t* lens, uint64_t* total) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || !total || (nchunks && !starts) || !valid_kind(gen_kind)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes) || !total || (nchunks && !starts) || !valid_kind(gen_kind)) return ANS_E_ARG;
     *total = 0;
     if (nchunks == 0) return ANS_OK;
     for (uint64_t c = 0; c < nchunks; ++c)
@@ -1744,41 +1647,31 @@ int ans_gpu_decode_var_chunks_ex(ans_gpu_table* gt, const uint8_t* in, uint64_t 
                                  const uint64_t* lens, uint64_t nchunks, const uint64_t* starts, int gen_kind,
                                  uint64_t seed, void* out, int sym_bytes) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || (nchunks && (!starts || !offsets || !lens)) || !valid_kind(gen_kind))
+    if (!gt || !valid_width_u32(sym_bytes) || (nchunks && (!starts || !offsets || !lens)) || !valid_kind(gen_kind))
         return ANS_E_ARG;
     if (nchunks == 0) return ANS_OK;
-    std::vector<uint32_t> l32(nchunks);
+    uint64_t maxlen = 0;
     for (uint64_t c = 0; c < nchunks; ++c) {
         if (starts[c + 1] < starts[c]) return ANS_E_ARG;
-        if (lens[c] > 0xffffffffull || offsets[c] > in_len || lens[c] > in_len - offsets[c]) return ANS_E_LEN;
-        l32[c] = static_cast<uint32_t>(lens[c]);
+        maxlen = std::max(maxlen, starts[c + 1] - starts[c]);
     }
+    std::vector<uint32_t> l32;
+    int rc = narrow_lens(offsets, lens, nchunks, in_len, l32);
+    if (rc) return rc;
     const uint64_t n = starts[nchunks];
     if ((n && !out) || (in_len && !in)) return ANS_E_ARG;
-    uint64_t maxlen = 0;
-    for (uint64_t c = 0; c < nchunks; ++c) maxlen = std::max(maxlen, starts[c + 1] - starts[c]);
     HIP_TRY(hipSetDevice(gt->g->device));
     const hipStream_t s = gt->g->stream;
-    DevBuf d_in, d_offs, d_lens, d_starts, d_out, d_status;
-    HIP_TRY(d_in.alloc(in_len + 128));  // the fast decoders read whole 128-B lines
-    HIP_TRY(d_offs.alloc(8 * nchunks));
-    HIP_TRY(d_lens.alloc(4 * nchunks));
+    DevStreams d;
+    DevBuf d_starts, d_out;
+    if ((rc = upload_streams(in, in_len, offsets, l32, s, d))) return rc;
     HIP_TRY(d_starts.alloc(8 * (nchunks + 1)));
     HIP_TRY(d_out.alloc(n * sym_bytes));
-    HIP_TRY(d_status.alloc(4));
-    if (in_len) HIP_TRY(hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_offs.p, offsets, 8 * nchunks, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_lens.p, l32.data(), 4 * nchunks, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_starts.p, starts, 8 * (nchunks + 1), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_status.p, 0, 4, s));
-    int rc = dev_decode_var(gt, static_cast<uint8_t*>(d_in.p), static_cast<uint64_t*>(d_offs.p), 0,
-                            static_cast<uint32_t*>(d_lens.p), nchunks, static_cast<uint64_t*>(d_starts.p), gen_kind,
-                            seed, d_out.p, sym_bytes, static_cast<uint32_t*>(d_status.p), s,
-                            staged_lmax(nchunks, maxlen, n, sym_bytes));
-    if (rc) return rc;
-    int st = 0;
-    if ((rc = ans_dev_status(gt->g, static_cast<uint32_t*>(d_status.p), s, &st))) return rc;
-    if (st) return st;
+    rc = dev_decode_var(gt, d.in.as<uint8_t>(), d.offs.as<uint64_t>(), 0, d.lens.as<uint32_t>(), nchunks,
+                        d_starts.as<uint64_t>(), gen_kind, seed, d_out.p, sym_bytes, d.status.as<uint32_t>(), s,
+                        staged_lmax(nchunks, maxlen, n, sym_bytes));
+    if (rc || (rc = read_status(gt->g, d.status.as<uint32_t>(), s))) return rc;
     if (n) HIP_TRY(hipMemcpy(out, d_out.p, n * sym_bytes, hipMemcpyDeviceToHost));
     return ANS_OK;
 } ANS_CATCH
@@ -1862,7 +1755,7 @@ int ans_gpu_encode_chunks_ex(ans_gpu_table* gt, const void* syms, int sym_bytes,
                              int gen_kind, uint64_t seed, uint8_t* out, uint64_t out_cap, uint64_t* offsets,
                              uint64_t* lens, uint64_t* total) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || chunk_len == 0 || !total || !valid_kind(gen_kind)) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes) || chunk_len == 0 || !total || !valid_kind(gen_kind)) return ANS_E_ARG;
     const fast::ChunkInit ini{gen_kind, seed};
     if (n && !syms) return ANS_E_ARG;
     if (gt->ts64) {
@@ -1880,17 +1773,14 @@ int ans_gpu_encode_chunks_ex(ans_gpu_table* gt, const void* syms, int sym_bytes,
     uint8_t* syms_dev = pipe_kernel_copies() ? mapped_ptr(syms) : nullptr;
     uint8_t* out_dev = out && syms_dev ? mapped_ptr(out) : nullptr;
     if (syms_dev && (!out || out_dev)) {
-        switch (sym_bytes) {
-        case 1: return pipe_encode_mapped<uint8_t>(gt, syms_dev, n, chunk_len, out_dev, out_cap, offsets, lens, total, ini);
-        case 2: return pipe_encode_mapped<uint16_t>(gt, syms_dev, n, chunk_len, out_dev, out_cap, offsets, lens, total, ini);
-        default: return pipe_encode_mapped<uint32_t>(gt, syms_dev, n, chunk_len, out_dev, out_cap, offsets, lens, total, ini);
-        }
+        return with_sym_type(sym_bytes, [&](auto t) {
+            return pipe_encode_mapped<decltype(t)>(gt, syms_dev, n, chunk_len, out_dev, out_cap, offsets, lens, total,
+                                                   ini);
+        });
     }
-    switch (sym_bytes) {
-    case 1: return pipe_encode<uint8_t>(gt, syms, n, chunk_len, out, out_cap, offsets, lens, total, ini);
-    case 2: return pipe_encode<uint16_t>(gt, syms, n, chunk_len, out, out_cap, offsets, lens, total, ini);
-    default: return pipe_encode<uint32_t>(gt, syms, n, chunk_len, out, out_cap, offsets, lens, total, ini);
-    }
+    return with_sym_type(sym_bytes, [&](auto t) {
+        return pipe_encode<decltype(t)>(gt, syms, n, chunk_len, out, out_cap, offsets, lens, total, ini);
+    });
 } ANS_CATCH
 
 int ans_gpu_encode_chunks(ans_gpu_table* gt, const void* syms, int sym_bytes, uint64_t n, uint64_t chunk_len,
@@ -1903,7 +1793,7 @@ int ans_gpu_decode_chunks_ex(ans_gpu_table* gt, const uint8_t* in, uint64_t in_l
                              const uint64_t* lens, uint64_t n, uint64_t chunk_len, int gen_kind, uint64_t seed,
                              void* out, int sym_bytes) try {
     (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width(sym_bytes) || chunk_len == 0) return ANS_E_ARG;
+    if (!gt || !valid_width_u32(sym_bytes) || chunk_len == 0) return ANS_E_ARG;
     const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
     if (nchunks && (!in || !offsets || !lens || !out)) return ANS_E_ARG;
     if (!valid_kind(gen_kind)) return ANS_E_ARG;
@@ -1912,61 +1802,41 @@ int ans_gpu_decode_chunks_ex(ans_gpu_table* gt, const uint8_t* in, uint64_t in_l
                                         seed, out, sym_bytes);
     const fast::ChunkInit ini{gen_kind, seed};
     if ((sym_bytes == 1 && gt->t.nsym > 256) || (sym_bytes == 2 && gt->t.nsym > 65536)) return ANS_E_ARG;
-    std::vector<uint32_t> l32(nchunks);
-    for (uint64_t j = 0; j < nchunks; ++j) {
-        if (lens[j] > 0xffffffffull || offsets[j] > in_len || lens[j] > in_len - offsets[j]) return ANS_E_LEN;
-        l32[j] = static_cast<uint32_t>(lens[j]);
-    }
+    std::vector<uint32_t> l32;
+    uint64_t slot_cap = 0, max_len = 0;
+    int rc = narrow_lens(offsets, lens, nchunks, in_len, l32, &max_len);
+    if (rc) return rc;
     // The fast decoders read the container in place (any stream alignment); slot_cap (widened
     // if a possibly corrupt stream is longer than a valid one can be) sizes the pipeline's
     // batches and tells a dense container from a scattered one.
-    uint64_t slot_cap = 0, max_len = 0;
     ans_gpu_slot_capacity(gt, chunk_len, &slot_cap);
-    for (uint64_t j = 0; j < nchunks; ++j) max_len = std::max<uint64_t>(max_len, l32[j]);
     slot_cap = std::max<uint64_t>(slot_cap, (max_len + 64 + 127) & ~uint64_t(127));
     HIP_TRY(hipSetDevice(gt->g->device));
     if (nchunks) {  // dense containers (the encoder's output) take the pipelined path
-        int rc = kPipeScattered;
         uint8_t* in_dev = pipe_kernel_copies() ? mapped_ptr(in) : nullptr;
         uint8_t* out_dev = in_dev ? mapped_ptr(out) : nullptr;
         if (in_dev && out_dev) {
-            switch (sym_bytes) {
-            case 1: rc = pipe_decode_mapped<uint8_t>(gt, in_dev, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out_dev, ini); break;
-            case 2: rc = pipe_decode_mapped<uint16_t>(gt, in_dev, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out_dev, ini); break;
-            default: rc = pipe_decode_mapped<uint32_t>(gt, in_dev, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out_dev, ini); break;
-            }
+            rc = with_sym_type(sym_bytes, [&](auto t) {
+                return pipe_decode_mapped<decltype(t)>(gt, in_dev, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind,
+                                                       out_dev, ini);
+            });
             if (rc != kPipeScattered) return rc;
         }
-        switch (sym_bytes) {
-        case 1: rc = pipe_decode<uint8_t>(gt, in, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out, ini); break;
-        case 2: rc = pipe_decode<uint16_t>(gt, in, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out, ini); break;
-        default: rc = pipe_decode<uint32_t>(gt, in, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out, ini); break;
-        }
+        rc = with_sym_type(sym_bytes, [&](auto t) {
+            return pipe_decode<decltype(t)>(gt, in, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out,
+                                            ini);
+        });
         if (rc != kPipeScattered) return rc;
     }
-    // streams scattered over the buffer: one upload of the whole input, decoded in place (+256:
-    // the fast decoders read whole aligned 128-B lines around each stream)
+    // streams scattered over the buffer: one upload of the whole input, decoded in place
     const hipStream_t s = gt->g->stream;
-    DevBuf d_in, d_off, d_lens, d_status, d_out;
-    HIP_TRY(d_in.alloc(in_len + 256));
-    HIP_TRY(d_off.alloc(nchunks * sizeof(uint64_t)));
-    HIP_TRY(d_lens.alloc(nchunks * sizeof(uint32_t)));
-    HIP_TRY(d_status.alloc(sizeof(uint32_t)));
+    DevStreams d;
+    DevBuf d_out;
+    if ((rc = upload_streams(in, in_len, offsets, l32, s, d))) return rc;
     HIP_TRY(d_out.alloc(n * sym_bytes));
-    if (in_len) HIP_TRY(hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, s));
-    if (nchunks) {
-        HIP_TRY(hipMemcpyAsync(d_off.p, offsets, nchunks * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_lens.p, l32.data(), nchunks * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemsetAsync(d_status.p, 0, sizeof(uint32_t), s));
-    int rc = ans_dev_decode_chunks_ex(gt, static_cast<uint8_t*>(d_in.p), static_cast<uint64_t*>(d_off.p), slot_cap,
-                                      static_cast<uint32_t*>(d_lens.p), n, chunk_len, gen_kind, seed, d_out.p,
-                                      sym_bytes, static_cast<uint32_t*>(d_status.p), s);
-    if (rc) return rc;
-    int st = 0;
-    rc = ans_dev_status(gt->g, static_cast<uint32_t*>(d_status.p), s, &st);
-    if (rc) return rc;
-    if (st) return st;
+    rc = ans_dev_decode_chunks_ex(gt, d.in.as<uint8_t>(), d.offs.as<uint64_t>(), slot_cap, d.lens.as<uint32_t>(), n,
+                                  chunk_len, gen_kind, seed, d_out.p, sym_bytes, d.status.as<uint32_t>(), s);
+    if (rc || (rc = read_status(gt->g, d.status.as<uint32_t>(), s))) return rc;
     if (n) HIP_TRY(hipMemcpy(out, d_out.p, n * sym_bytes, hipMemcpyDeviceToHost));
     return ANS_OK;
 } ANS_CATCH
