@@ -455,7 +455,11 @@ int ans_gpu_dense_sets_decode(ans_gpu_table *gt, uint64_t num_graphs, const uint
  *      labels (src/graph_codec.rs:31-34, 61-65); its stream is that message flattened.
  *      Edges are uint32 pairs in the alphabet of section 5 (undirected: i <= j); an edge outside
  *      it, or with labelled edges a pair given twice, is ANS_E_SYMBOL; a label outside its table
- *      is ANS_E_SYMBOL.  Decode pops node labels, the indicator vector, then as many edge labels
+ *      is ANS_E_SYMBOL.  Required lengths, which the library cannot check and reads in full:
+ *      with a node table, node_labels holds sum(num_nodes) entries (num_nodes[g] per graph, no
+ *      gaps); with an edge table, edge_labels holds edge_offsets[num_graphs] entries, entry k the
+ *      label of edge k (one per edge of every graph); edges holds 2 * edge_offsets[num_graphs]
+ *      entries.  A shorter buffer is read past its end.  Decode pops node labels, the indicator vector, then as many edge labels
  *      as the vector holds edges (src/graph_codec.rs:36-38, 67-71) and returns every graph's
  *      edges sorted by (i, j) -- EdgesIID::pop's `indices.sort_unstable()` -- with their labels
  *      beside them, graph after graph; edge_offsets (num_graphs + 1) gives each graph's range;

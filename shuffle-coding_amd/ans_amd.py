@@ -1156,8 +1156,9 @@ class GpuDenseSets:
                                                _np_ptr(lens), ctypes.byref(total)), "ans_gpu_dense_sets_encode")
         return out[:total.value], offsets[:len(nn)], lens[:len(nn)]
 
-    def decode(self, num_nodes, data, offsets, lens, cap=None):
-        """Returns the per-graph edge arrays (alphabet order)."""
+    def decode(self, num_nodes, data, offsets, lens, cap=None, return_offsets=False):
+        """Returns the per-graph edge arrays (alphabet order); with return_offsets also the
+        library's edge_offsets array (num_graphs + 1 entries) they were sliced by."""
         nn = np.ascontiguousarray(np.asarray(num_nodes, dtype=np.uint32))
         data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8))
         offsets = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
@@ -1176,7 +1177,8 @@ class GpuDenseSets:
                 cap = int(eo[-1])
                 continue
             _check(rc, "ans_gpu_dense_sets_decode")
-            return [edges[int(eo[g]):int(eo[g + 1])] for g in range(len(nn))]
+            out = [edges[int(eo[g]):int(eo[g + 1])] for g in range(len(nn))]
+            return (out, eo) if return_offsets else out
         raise AnsError(ANS_E_LEN, "ans_gpu_dense_sets_decode")
 
 
@@ -1285,11 +1287,18 @@ class GpuGraphs:
 
     def encode(self, graphs, gen_kind=GEN_ZEROS, seed=0):
         """graphs: per graph (num_nodes, node_labels or None, edges (m, 2), edge_labels or None).
+        With a node codec every graph needs num_nodes node labels, with an edge-label codec one
+        label per edge: the library reads that many, so anything else is ANS_E_ARG here.
         Returns (bytes, offsets, lens), one stream per graph."""
         nn = np.ascontiguousarray(np.asarray([int(g[0]) for g in graphs], dtype=np.uint32))
         nl = [np.asarray(g[1] if g[1] is not None else np.zeros(0), dtype=np.uint32).reshape(-1) for g in graphs]
         parts = [np.asarray(g[2], dtype=np.uint32).reshape(-1, 2) for g in graphs]
         el = [np.asarray(g[3] if g[3] is not None else np.zeros(0), dtype=np.uint32).reshape(-1) for g in graphs]
+        for k, g in enumerate(graphs):
+            if self.node_cat is not None and (g[1] is None or len(nl[k]) != int(nn[k])):
+                raise AnsError(ANS_E_ARG, f"GpuGraphs.encode: graph {k} needs {int(nn[k])} node labels")
+            if self.edge_cat is not None and (g[3] is None or len(el[k]) != len(parts[k])):
+                raise AnsError(ANS_E_ARG, f"GpuGraphs.encode: graph {k} needs {len(parts[k])} edge labels")
         eo = np.zeros(len(parts) + 1, np.uint64)
         eo[1:] = np.cumsum([len(p) for p in parts])
         edges = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 2), np.uint32))
@@ -1309,8 +1318,9 @@ class GpuGraphs:
                                            _np_ptr(lens), ctypes.byref(total)), "ans_gpu_graphs_encode")
         return out[:total.value], offsets[:len(nn)], lens[:len(nn)]
 
-    def decode(self, num_nodes, data, offsets, lens, cap=None, gen_kind=GEN_ZEROS, seed=0):
-        """Per graph (node_labels or None, edges sorted by (i, j), edge_labels or None)."""
+    def decode(self, num_nodes, data, offsets, lens, cap=None, gen_kind=GEN_ZEROS, seed=0, return_offsets=False):
+        """Per graph (node_labels or None, edges sorted by (i, j), edge_labels or None); with
+        return_offsets also the library's edge_offsets array (num_graphs + 1 entries)."""
         nn = np.ascontiguousarray(np.asarray(num_nodes, dtype=np.uint32))
         data, offsets, lens = _dec_arrays(data, offsets, lens)
         slots = sum(self._sizes(nn))
@@ -1336,7 +1346,7 @@ class GpuGraphs:
                 a, b = int(eo[g]), int(eo[g + 1])
                 out.append((node_labels[no[g]:no[g + 1]].copy() if self.node_cat is not None else None,
                             edges[a:b].copy(), edge_labels[a:b].copy() if self.edge_cat is not None else None))
-            return out
+            return (out, eo) if return_offsets else out
         raise AnsError(ANS_E_LEN, "ans_gpu_graphs_decode")
 
 

@@ -232,15 +232,17 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_emit_multi(uint32_t direc
     }
 }
 
-// per graph: set slots before S[g] (tile base + the partial tile), i.e. graph g's first edge
-__global__ __launch_bounds__(256) void k_graph_edge_offsets(const uint8_t* __restrict__ dense,
+// per graph: set slots before S[g] (tile base + the partial tile), i.e. graph g's first edge.
+// A graph starting at the end of the vector (trailing zero-slot graphs, S[g] == len) gets the
+// total: with len a multiple of the tile its tile index would be ntiles, one past base.
+__global__ __launch_bounds__(256) void k_graph_edge_offsets(const uint8_t* __restrict__ dense, uint64_t len,
                                                             const uint64_t* __restrict__ S, uint64_t num_graphs,
                                                             const uint64_t* __restrict__ base,
                                                             const uint64_t* __restrict__ total,
                                                             uint64_t* __restrict__ edge_offsets) {
     const uint64_t g = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (g > num_graphs) return;
-    if (g == num_graphs) {
+    if (g == num_graphs || S[g] >= len) {
         edge_offsets[g] = *total;
         return;
     }
@@ -678,9 +680,9 @@ int ans_gpu_dense_sets_decode(ans_gpu_table* gt, uint64_t num_graphs, const uint
             directed ? 1u : 0u, loops ? 1u : 0u, d_nn.as<uint32_t>(), d_S.as<uint64_t>(), num_graphs,
             d_dense.as<uint8_t>(), len, base, d_edges.as<uint32_t>(), cap, d.status.as<uint32_t>());
         HIP_TRY(hipGetLastError());
-        k_graph_edge_offsets<<<blocks_for(num_graphs + 1, 256), 256, 0, s>>>(d_dense.as<uint8_t>(), d_S.as<uint64_t>(),
-                                                                           num_graphs, base, d_total,
-                                                                           d_eo.as<uint64_t>());
+        k_graph_edge_offsets<<<blocks_for(num_graphs + 1, 256), 256, 0, s>>>(d_dense.as<uint8_t>(), len,
+                                                                           d_S.as<uint64_t>(), num_graphs, base,
+                                                                           d_total, d_eo.as<uint64_t>());
         HIP_TRY(hipGetLastError());
     }
     int st = 0;
@@ -859,7 +861,7 @@ int ans_gpu_graphs_decode(ans_gpu_tableset* ts, uint32_t node_table, uint32_t ed
         k_excl_scan<<<1, 1024, 0, s>>>(counts, ntiles, base, d_total);
         HIP_TRY(hipGetLastError());
         k_graph_edge_offsets<<<blocks_for(num_graphs + 1, 256), 256, 0, s>>>(
-            d_rdense.as<uint8_t>(), d_S.as<uint64_t>(), num_graphs, base, d_total, d_eo.as<uint64_t>());
+            d_rdense.as<uint8_t>(), len, d_S.as<uint64_t>(), num_graphs, base, d_total, d_eo.as<uint64_t>());
         HIP_TRY(hipGetLastError());
         k_graph_emit_rows<<<static_cast<unsigned>(ntiles), kTileThreads, 0, s>>>(
             directed ? 1u : 0u, loops ? 1u : 0u, d_nn.as<uint32_t>(), d_S.as<uint64_t>(), num_graphs,
