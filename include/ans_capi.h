@@ -395,6 +395,70 @@ int ans_dev_independent_decode_var(ans_gpu_tableset *ts, const uint8_t *d_tids, 
                                    uint64_t nchunks, const uint64_t *d_starts, int gen_kind, uint64_t seed,
                                    void *d_syms, int sym_bytes, uint32_t *d_status, void *stream);
 
+/* Resume: push onto, or pop from, the message ALREADY in each chunk's slot -- the reference's
+ * push(&mut Message, x) / pop(&mut Message) on any message (src/ans.rs:96-116), which bits-back
+ * coding, codecs of different alphabets composed on one message (GraphIID, src/graph_codec.rs:31-34)
+ * and appending to a compressed message rest on.  Chunk c's input message is
+ * Message::unflatten(bytes of slot c, d_lens[c] of them) with the Empty tail generator: head 0, so
+ * the first operation's renorm_up pulls from the top of the bytes (zero bytes on top of a message
+ * are consumed by that pull).  ZEROS and RANDOM tails are out of scope: a byte container cannot carry
+ * the tail's num_generated.  A pull past the stream's start sets ANS_E_EXHAUSTED in *d_status and
+ * d_lens[c] = 0, and leaves that slot's contents unspecified.
+ *   push: Independent::push of the chunk's symbols, last first (src/codec.rs:388-391), then
+ *         flatten (src/ans.rs:255-260) back into the slot; d_lens[c] = the new length.
+ *   pop:  the chunk's symbols by forward pops (src/codec.rs:393-399) into d_syms, then flatten
+ *         of what remains back into the slot; d_lens[c] = the new length.
+ * The bytes equal the reference's flatten() byte for byte, the single 0x00 it writes for a head
+ * of 0 included: a chunk of zero symbols grows by one zero byte (flatten(unflatten(B)) = B ++ [0]).
+ * Push needs slot_cap >= d_lens[c] + ans_gpu_tableset_slot_capacity(ts, chunk_len) (the longest
+ * chunk's for _var) to be sure of room; a chunk whose result would pass slot_cap, or whose d_lens[c]
+ * is already above it, is ANS_E_LEN with d_lens[c] = 0.  Pop needs slot_cap >= 16 (a result is at
+ * most one byte longer than its input).  slot_cap may be any value otherwise, and d_slots at any
+ * alignment.  Any set of at most 256 tables, any chunk length, fixed or variable chunks: the exact
+ * 64-bit kernels (one lane per chunk) take them all.  ans_dev_independent_push and _pop run their
+ * full chunks on the fast kernels instead where ans_gpu_tableset_fast != 0, chunk_len * sym_bytes
+ * % 128 == 0, slot_cap % 128 == 0, slot_cap < 2^27 and d_syms, d_tids, d_slots are 16-byte aligned.
+ * The ragged last chunk still goes to the exact kernel, and so does a message the fast kernels
+ * cannot start from: for a push one too short to fill the 2^56 head (fewer than eight significant
+ * bytes), for a pop one with zero bytes on top or too short for the first pull.  Both paths give the
+ * same bytes. */
+int ans_dev_independent_push(ans_gpu_tableset *ts, const uint8_t *d_tids, const void *d_syms, int sym_bytes,
+                             uint64_t n, uint64_t chunk_len, uint8_t *d_slots, uint64_t slot_cap,
+                             uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_independent_pop(ans_gpu_tableset *ts, const uint8_t *d_tids, uint8_t *d_slots /* in/out */,
+                            uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint64_t n, uint64_t chunk_len,
+                            void *d_syms, int sym_bytes, uint32_t *d_status, void *stream);
+int ans_dev_independent_push_var(ans_gpu_tableset *ts, const uint8_t *d_tids, const void *d_syms, int sym_bytes,
+                                 uint64_t nchunks, const uint64_t *d_starts, uint8_t *d_slots, uint64_t slot_cap,
+                                 uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_independent_pop_var(ans_gpu_tableset *ts, const uint8_t *d_tids, uint8_t *d_slots /* in/out */,
+                                uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint64_t nchunks,
+                                const uint64_t *d_starts, void *d_syms, int sym_bytes, uint32_t *d_status,
+                                void *stream);
+/* ... on host buffers, synchronous: the input messages come as a dense container (chunk c at
+ * in[in_offsets[c] .. + in_lens[c]), one entry per chunk) and the results leave as one: chunk c
+ * at out[offsets[c] .. + lens[c]).  out == NULL is the size query (*total is set, no container
+ * written; pop still fills out_syms); out_cap < *total is ANS_E_LEN.  table_ids are u32 per position
+ * as in the calls above. */
+int ans_gpu_independent_push_chunks(ans_gpu_tableset *ts, const uint32_t *table_ids, const void *syms, int sym_bytes,
+                                    uint64_t n, uint64_t chunk_len, const uint8_t *in, uint64_t in_len,
+                                    const uint64_t *in_offsets, const uint64_t *in_lens, uint8_t *out,
+                                    uint64_t out_cap, uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_independent_pop_chunks(ans_gpu_tableset *ts, const uint32_t *table_ids, const uint8_t *in, uint64_t in_len,
+                                   const uint64_t *in_offsets, const uint64_t *in_lens, uint64_t n, uint64_t chunk_len,
+                                   void *out_syms, int sym_bytes, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
+                                   uint64_t *lens, uint64_t *total);
+int ans_gpu_independent_push_var_chunks(ans_gpu_tableset *ts, const uint32_t *table_ids, const void *syms,
+                                        int sym_bytes, uint64_t nchunks, const uint64_t *starts, const uint8_t *in,
+                                        uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens,
+                                        uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
+                                        uint64_t *total);
+int ans_gpu_independent_pop_var_chunks(ans_gpu_tableset *ts, const uint32_t *table_ids, const uint8_t *in,
+                                       uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens,
+                                       uint64_t nchunks, const uint64_t *starts, void *out_syms, int sym_bytes,
+                                       uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
+                                       uint64_t *total);
+
 /* ======================================================================
  * (5) Graph models' bulk-IID caller — DenseSetIID<EdgeIndex, AllEdgeIndices> with an
  *     IID<Bernoulli> (ErdosRenyi, src/graph_codec.rs:105-205).  Edges are uint32 pairs

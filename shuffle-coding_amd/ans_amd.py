@@ -138,6 +138,14 @@ SIGNATURES = {
     "ans_gpu_independent_decode_var_chunks": (ci, [vp, vp, vp, u64, vp, vp, u64, vp, ci, u64, vp, ci]),
     "ans_dev_independent_encode_var": (ci, [vp, vp, vp, ci, u64, vp, ci, u64, vp, u64, vp, vp, vp]),
     "ans_dev_independent_decode_var": (ci, [vp, vp, vp, vp, u64, vp, u64, vp, ci, u64, vp, ci, vp, vp]),
+    "ans_dev_independent_push": (ci, [vp, vp, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
+    "ans_dev_independent_pop": (ci, [vp, vp, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
+    "ans_dev_independent_push_var": (ci, [vp, vp, vp, ci, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_independent_pop_var": (ci, [vp, vp, vp, u64, vp, u64, vp, vp, ci, vp, vp]),
+    "ans_gpu_independent_push_chunks": (ci, [vp, vp, vp, ci, u64, u64, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_independent_pop_chunks": (ci, [vp, vp, vp, u64, vp, vp, u64, u64, vp, ci, vp, u64, vp, vp, u64p]),
+    "ans_gpu_independent_push_var_chunks": (ci, [vp, vp, vp, ci, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_independent_pop_var_chunks": (ci, [vp, vp, vp, u64, vp, vp, u64, vp, vp, ci, vp, u64, vp, vp, u64p]),
     "ans_gpu_graphs_encode": (ci, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ci, ci, u64, vp, vp, vp, vp,
                                    vp, ci, u64, vp, u64, vp, vp, u64p]),
     "ans_gpu_graphs_decode": (ci, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ci, ci, u64, vp, vp, u64, vp,
@@ -982,6 +990,99 @@ class GpuTableSet:
                                                            _WIDTH[np.dtype(dtype)]),
                "ans_gpu_independent_decode_var_chunks")
         return out[:n]
+
+    # ---- resume (include/ans_capi.h 4b): push onto / pop from existing per-chunk messages, each
+    # Message::unflatten(bytes) with the Empty generator.  Argument lengths are checked here,
+    # before any pointer reaches the library (it reads every array in full).
+    @staticmethod
+    def _resume_container(where, data, offsets, lens, nchunks):
+        data, offsets, lens = _dec_arrays(data, offsets, lens)
+        if data.ndim != 1 or offsets.shape != (nchunks,) or lens.shape != (nchunks,):
+            raise AnsError(ANS_E_ARG, f"{where}: the container needs {nchunks} offsets and lens (one per chunk)")
+        if nchunks and int((offsets + lens).max()) > data.size:
+            raise AnsError(ANS_E_LEN, f"{where}: a message ends past the {data.size} container bytes")
+        return data, offsets, lens
+
+    @staticmethod
+    def _resume_starts(where, starts, n):
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.uint64))
+        if st.ndim != 1 or len(st) < 1 or int(st[0]) != 0 or int(st[-1]) != n or np.any(st[1:] < st[:-1]):
+            raise AnsError(ANS_E_ARG, f"{where}: starts must rise from 0 to the {n} positions")
+        return st
+
+    def _resume_call(self, where, fn, args_before, args_after, nchunks, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(nchunks, 1), np.uint64)
+        lens = np.zeros(max(nchunks, 1), np.uint64)
+        total = u64(0)
+        _check(fn(self.h, *args_before, *args_after, _np_ptr(out), len(out), _np_ptr(offsets), _np_ptr(lens),
+                  ctypes.byref(total)), where)
+        return out[:total.value], offsets[:nchunks], lens[:nchunks]
+
+    def _push(self, where, fn, table_ids, syms, shape_args, nchunks, longest, data, offsets, lens):
+        syms = np.ascontiguousarray(syms)
+        tids = np.ascontiguousarray(np.asarray(table_ids, dtype=np.uint32))
+        if syms.ndim != 1 or tids.shape != syms.shape:
+            raise AnsError(ANS_E_ARG, f"{where}: {len(tids)} table ids for {len(syms)} symbols")
+        data, offsets, lens = self._resume_container(where, data, offsets, lens, nchunks)
+        cap = data.size + nchunks * self.slot_capacity(max(longest, 1))
+        return self._resume_call(where, fn, (_np_ptr(tids), _np_ptr(syms), _WIDTH[syms.dtype]) + shape_args,
+                                 (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens)),
+                                 nchunks, cap)
+
+    def _pop(self, where, fn, table_ids, shape_args, nchunks, data, offsets, lens, dtype):
+        tids = np.ascontiguousarray(np.asarray(table_ids, dtype=np.uint32))
+        data, offsets, lens = self._resume_container(where, data, offsets, lens, nchunks)
+        syms = np.zeros(max(len(tids), 1), dtype)
+        container = self._resume_call(
+            where, fn, (_np_ptr(tids), _np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens)),
+            shape_args + (_np_ptr(syms), _WIDTH[np.dtype(dtype)]), nchunks, data.size + 16 * nchunks)
+        return syms[:len(tids)], container
+
+    def push_chunks(self, table_ids, syms, chunk_len, data, offsets, lens):
+        """Independent::push of chunk c's symbols [c*chunk_len, ...) onto message c of the
+        container (data, offsets, lens), then flatten: returns the container of the results."""
+        if chunk_len <= 0:
+            raise AnsError(ANS_E_ARG, "push_chunks: chunk_len must be positive")
+        n = len(syms)
+        return self._push("ans_gpu_independent_push_chunks", lib().ans_gpu_independent_push_chunks, table_ids, syms,
+                          (n, chunk_len), -(-n // chunk_len), chunk_len, data, offsets, lens)
+
+    def pop_chunks(self, table_ids, data, offsets, lens, chunk_len, dtype=np.uint32):
+        """chunk_len forward pops from every message (len(table_ids) positions in all): returns
+        (syms, container of what remains)."""
+        if chunk_len <= 0:
+            raise AnsError(ANS_E_ARG, "pop_chunks: chunk_len must be positive")
+        n = len(table_ids)
+        return self._pop("ans_gpu_independent_pop_chunks", lib().ans_gpu_independent_pop_chunks, table_ids,
+                         (n, chunk_len), -(-n // chunk_len), data, offsets, lens, dtype)
+
+    def push_var_chunks(self, table_ids, syms, starts, data, offsets, lens):
+        """push_chunks over variable chunks: chunk c = positions [starts[c], starts[c+1])."""
+        where = "ans_gpu_independent_push_var_chunks"
+        st = self._resume_starts(where, starts, len(syms))
+        nchunks = len(st) - 1
+        longest = int(np.max(np.diff(st))) if nchunks else 0
+        return self._push(where, lib().ans_gpu_independent_push_var_chunks, table_ids, syms, (nchunks, _np_ptr(st)),
+                          nchunks, longest, data, offsets, lens)
+
+    def pop_var_chunks(self, table_ids, data, offsets, lens, starts, dtype=np.uint32):
+        where = "ans_gpu_independent_pop_var_chunks"
+        st = self._resume_starts(where, starts, len(table_ids))
+        nchunks = len(st) - 1
+        return self._pop(where, lib().ans_gpu_independent_pop_var_chunks, table_ids, (nchunks, _np_ptr(st)), nchunks,
+                         data, offsets, lens, dtype)
+
+    def dev_push(self, d_tids, d_syms, sym_bytes, n, chunk_len, d_slots, slot_cap, d_lens, d_status, stream=None):
+        """In place on device slots: d_lens is read and rewritten; d_tids one byte per position."""
+        _check(lib().ans_dev_independent_push(self.h, _dptr(d_tids), _dptr(d_syms), sym_bytes, n, chunk_len,
+                                              _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_independent_push")
+
+    def dev_pop(self, d_tids, d_slots, slot_cap, d_lens, n, chunk_len, d_syms, sym_bytes, d_status, stream=None):
+        _check(lib().ans_dev_independent_pop(self.h, _dptr(d_tids), _dptr(d_slots), slot_cap, _dptr(d_lens), n,
+                                             chunk_len, _dptr(d_syms), sym_bytes, _dptr(d_status), _sptr(stream)),
+               "ans_dev_independent_pop")
 
     def fast(self):
         """1 / 2: the set runs on the fast kernels (2: with voted exact renorm rows); 0: exact only."""

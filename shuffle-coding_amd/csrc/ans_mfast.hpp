@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "ans_fast.hpp"
+#include "ans_resume.hpp"
 
 namespace shuffle_coding {
 namespace mfast {
@@ -270,7 +271,28 @@ __device__ __forceinline__ void unit_put(uint4& v, int j, uint32_t lo, uint32_t 
 // Symbols (and table ids) come in 128-B groups per lane (64 B for 1,024 lanes), walked last to first; a point (the
 // page flush) precedes every SPP symbols, which emit at most 64 bytes between them.
 // kL: the layout (EncLayout; the model's tables must be built for it, Model::kTabE).
-template <class Model, typename Sym, int SPP, int kL = kLanes>
+// kRes: resume (ans_dev_independent_push).  The chunk's initial message is
+// Message::unflatten(slot bytes [0, lens[c])) with the Empty generator instead of ini's, and the
+// result goes back into the slot:
+//  * the prologue pulls the message's top bytes until head >= 2^56 (ans_resume.hpp).  That is
+//    the reference's first renorm: every pK <= 2^56, so the first push takes no byte back, its
+//    renorm_down re-emits whatever the prologue pulled beyond the reference's renorm_up (the
+//    message's byte prefixes are monotone: one position has its head in [pK, 2^8 pK)), and the
+//    renorm word's precondition (head >= Hmin) holds;
+//  * a message too short to reach 2^56 does not meet that precondition: the lane leaves its slot
+//    as it is and sets kResumeExact in lens[c], and the exact kernel (ans_codecs.hip k_push64)
+//    codes those chunks after this kernel;
+//  * the position starts at the bytes left, not 0, with page fp = (pos - 1) / 64 (the first one
+//    not a byte behind the position: a take-back may reach byte pos - 1) loaded into the ring
+//    and, if fp is odd, its even partner into MPageOut's held page; the pages below stay
+//    untouched in the slot;
+//  * after the prologue the head is at least 2^56 and only grows until a push emits, so a
+//    take-back only ever returns a byte this call emitted: it never reaches below the start
+//    position (fp = (pos - 1) / 64 is therefore one page more careful than needed) and never
+//    below byte 0.  The kErrPulled arm, which would be the Empty generator (ANS_E_EXHAUSTED), is
+//    kept for the skeleton's sake and cannot be taken here.
+constexpr uint32_t kResumeExact = 0x80000000u;
+template <class Model, typename Sym, int SPP, int kL = kLanes, bool kRes = false>
 __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, const Sym* __restrict__ syms,
                                                                    const uint8_t* __restrict__ tids, uint64_t chunk_len,
                                                                    uint64_t nfull, uint8_t* __restrict__ slots,
@@ -310,6 +332,41 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, con
     e.f = MFunnelT<kL>{0, 0, 0, ring.col, ring.col};
     e.err = 0;
     uint32_t fp = 0, over = 0;
+    if constexpr (kRes) {
+        const uint32_t len0 = lens[c];
+        if (len0 > slot_cap) {
+            atomicOr(status, 1u << ANS_E_LEN);
+            lens[c] = 0;
+            return;
+        }
+        uint32_t pos = len0;
+        e.head = resume::pull_to_full(dst, pos);
+        if (e.head < kMaxMinHead) {
+            lens[c] = len0 | kResumeExact;
+            return;
+        }
+        fp = resume::first_open_page(pos);
+        const uint4* line = reinterpret_cast<const uint4*>(dst + 128ull * (fp >> 1));
+        const int o = (fp & 1) ? 4 : 0;
+        if (fp & 1) {
+            pout.h0 = line[0];
+            pout.h1 = line[1];
+            pout.h2 = line[2];
+            pout.h3 = line[3];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint4 v = line[o + k];
+            ring.at(static_cast<int32_t>(16 * fp + 4 * k)) = v.x;
+            ring.at(static_cast<int32_t>(16 * fp + 4 * k + 1)) = v.y;
+            ring.at(static_cast<int32_t>(16 * fp + 4 * k + 2)) = v.z;
+            ring.at(static_cast<int32_t>(16 * fp + 4 * k + 3)) = v.w;
+        }
+        // (dword pos / 4 with its pos & 3 bytes: the first dword of the next page when pos = 64 fp + 64,
+        // none of whose bytes count)
+        e.f = MFunnelT<kL>{ring.at(static_cast<int32_t>(pos >> 2)), 8 * pos, 0u - 8 * pos,
+                           EncLayout<kL>::row_of(8 * pos, ring.col), ring.col};
+    }
     // page fp leaves once the position is a byte past it: a take-back never reaches a flushed page
     auto flush_ready = [&]() __attribute__((always_inline)) {
         if (e.f.pos8 >= 512u * fp + 520u) {
@@ -414,7 +471,7 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, con
     if (err & kErrZeroMass) err = md.classify(syms + c * chunk_len, tsrc, chunk_len, err);
     if (err) {
         const int code = (err & kErrSymbol) ? ANS_E_SYMBOL : (err & kErrNormRange) ? ANS_E_NORM_RANGE
-                         : (err & kErrZeroMass) ? ANS_E_ZERO_MASS : ANS_E_MISMATCH;
+                         : (err & kErrZeroMass) ? ANS_E_ZERO_MASS : kRes ? ANS_E_EXHAUSTED : ANS_E_MISMATCH;
         atomicOr(status, 1u << code);
     }
     if (over) atomicOr(status, 1u << ANS_E_LEN);
@@ -427,7 +484,14 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, con
 // whose pops can take more than four bytes (Uniform and LogUniform sizes up to 2^46).
 __device__ const uint4 kZeroPair[8] = {};  // the Zeros tail generator's bytes below a stream
 
-template <int kL>
+// kRes: the chain of a resumed message (k_mdec<kRes>, ans_dev_independent_pop).  A byte that
+// renorm_down hands back is then new data, not the stream's own (the head of an unflattened
+// message was never a stream byte): it is STORED in the ring (and row 0's mirror) instead of
+// compared.  Hand-backs are at most one byte above the running minimum, so at most one is ever
+// live, and only as the byte just below the final position: the epilogue copies that byte from
+// the ring to the slot (top_byte; the stream's own byte again when nothing is pending).  `bad`
+// there means a hand-back while the position was below byte 0: the Empty generator had been read.
+template <int kL, bool kRes = false>
 struct MChainT {
     using Lay = DecLayout<kL>;
     const uint8_t* src;
@@ -506,6 +570,11 @@ struct MChainT {
         wx = lds_ld32(a + Lay::kRing + 4 * kL);
     }
     __device__ __forceinline__ void form_window() { W = __builtin_amdgcn_alignbit(wx, wy, static_cast<uint32_t>(P8)); }
+    // the byte just below the position (stream byte P + 3, the window's top), as the ring holds it
+    __device__ __forceinline__ uint32_t top_byte() const {
+        const int32_t p8 = P8 + 24;
+        return (lds_ld32(row_addr(p8) + Lay::kRing) >> (static_cast<uint32_t>(p8) & 24u)) & 0xFFu;
+    }
     __device__ __forceinline__ void start(const uint8_t* s, int32_t len) {
         src = s;
         bad = false;
@@ -573,8 +642,17 @@ struct MChainT {
                 m8 -= 8;
                 if (m == 0) {  // renorm_down: byte xj0 & 0xFF back onto the stream at P + 4
                     const int32_t p8 = P8 + 32;
-                    const uint32_t byte = (lds_ld32(row_addr(p8) + Lay::kRing) >> (static_cast<uint32_t>(p8) & 31u)) & 0xFFu;
-                    bad |= byte != (xj0 & 0xFFu);
+                    if constexpr (kRes) {
+                        const uint32_t a = row_addr(p8) + Lay::kRing, sh = static_cast<uint32_t>(p8) & 24u;
+                        const uint32_t d = (lds_ld32(a) & ~(0xFFu << sh)) | ((xj0 & 0xFFu) << sh);
+                        *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(a)) = d;
+                        if ((static_cast<uint32_t>(p8) & 0x3E0u) == 0)  // row 0: its mirror too
+                            *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(col + Lay::kRing + 32u * kL * 4)) = d;
+                        bad |= p8 < 0;
+                    } else {
+                        const uint32_t byte = (lds_ld32(row_addr(p8) + Lay::kRing) >> (static_cast<uint32_t>(p8) & 31u)) & 0xFFu;
+                        bad |= byte != (xj0 & 0xFFu);
+                    }
                 }
             }
         }
@@ -604,7 +682,16 @@ using MChain = MChainT<kLanes>;
 // bytes between points, so no window read reaches an unlanded page).
 // kL: the layout (DecLayout: 256 lanes, or 1,024 sharing one table image at LDS offset 0; the
 // model's tables must be built for it, Model::kTab).
-template <class Model, typename Sym, int SPP, int kL = kLanes>
+// kRes: resume (ans_dev_independent_pop; slots in place, offsets NULL).  The message is
+// Message::unflatten(slot bytes) with the Empty generator and nothing is compared with an initial
+// message at the end: the epilogue writes the pending handed-back byte (MChainT<kRes>) and the
+// head's bytes, low first (flatten, src/ans.rs:255-260), at the final position and sets lens[c].
+// The bytes below that position are the slot's own and stay.  A lane whose first pull does not
+// reach the first pop's bound within the unflatten's nine bytes (zero bytes on top of the
+// message) or runs below byte 0 sets kResumeExact in lens[c] and leaves slot and symbols to the
+// exact kernel (k_pop64, which also reports the exhaustion); a position below byte 0 later on is
+// ANS_E_EXHAUSTED (src/ans.rs:144).
+template <class Model, typename Sym, int SPP, int kL = kLanes, bool kRes = false>
 __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, const uint8_t* __restrict__ slots,
                                                                    uint64_t slot_cap,
                                                                    const uint64_t* __restrict__ offsets,
@@ -627,12 +714,20 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, con
 
     if ((!offsets && lens[c] > slot_cap) || lens[c] >= (1u << 27)) {
         atomicOr(status, 1u << ANS_E_LEN);
+        if constexpr (kRes) const_cast<uint32_t*>(lens)[c] = 0;
         return;
     }
-    MChainT<kL> ch;
+    MChainT<kL, kRes> ch;
     ch.col = 4 * threadIdx.x;
     ch.start(slots + (offsets ? offsets[c] : c * slot_cap), static_cast<int32_t>(lens[c]));
-    ch.pull_until(md.first_bound(tsrc));  // Message::unflatten: head 0, the first pop's renorm_up
+    const uint64_t bound0 = md.first_bound(tsrc);
+    ch.pull_until(bound0);  // Message::unflatten: head 0, the first pop's renorm_up
+    if constexpr (kRes) {
+        if (ch.head < bound0 || ch.P8 < -32) {
+            const_cast<uint32_t*>(lens)[c] = lens[c] | kResumeExact;
+            return;
+        }
+    }
     typename Model::DecState ds;
     md.dec_init(ds);
 
@@ -654,7 +749,8 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, con
     // 16 VGPRs for the pair as for one line before (holding a whole 128-B load spilled at 1,024
     // lanes' 128 VGPRs), and a line's id is one v_bfe at nibble 4 * (line & 1).  (Not for
     // kNormSmall sets, Model::kPairIds: their longer pop leaves no room for it, 12-20 B spilled.)
-    constexpr bool kPair = Model::kTids && kL == kLanesW && Model::kPairIds;
+    // (Nor for resume pops, kRes: with the pair the u8 variants spilled 12-28 B a lane at 128 VGPRs.)
+    constexpr bool kPair = Model::kTids && kL == kLanesW && Model::kPairIds && !kRes;
     constexpr int TW = LU * U / 4;  // u32 words of ids per line
     uint32_t tl[TW], tn[TW];
 #pragma unroll
@@ -743,6 +839,24 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, con
         uint4* d = dst + (nunit - LU);
 #pragma unroll
         for (int k = 0; k < LU; ++k) d[k] = q[k];
+    }
+    if constexpr (kRes) {
+        uint32_t* const lens_out = const_cast<uint32_t*>(lens);
+        uint8_t* const slot = const_cast<uint8_t*>(ch.src);  // (offsets == NULL: slots + c * slot_cap)
+        const int32_t rem = (ch.P8 >> 3) + 4;  // bytes of the stream left; < 0: the generator was read
+        const uint32_t nb = (71u - static_cast<uint32_t>(__builtin_clzll(ch.head | 1))) >> 3;  // head bytes, >= 1
+        if (rem < 0 || ch.bad) {
+            atomicOr(status, 1u << ANS_E_EXHAUSTED);
+            lens_out[c] = 0;
+        } else if (static_cast<uint64_t>(rem) + nb > slot_cap) {
+            atomicOr(status, 1u << ANS_E_LEN);
+            lens_out[c] = 0;
+        } else {
+            if (rem > 0) slot[rem - 1] = static_cast<uint8_t>(ch.top_byte());  // a pending handed-back byte
+            for (uint32_t k = 0; k < nb; ++k) slot[rem + k] = static_cast<uint8_t>(ch.head >> (8 * k));
+            lens_out[c] = static_cast<uint32_t>(rem) + nb;
+        }
+        return;
     }
     // assert_eq!(initial, m) (src/ans.rs:56, 302-310)
     ch.pull_until(kMaxMinHead);

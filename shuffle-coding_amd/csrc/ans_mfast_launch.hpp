@@ -11,16 +11,16 @@ namespace mfast {
 
 inline unsigned mgrid(uint64_t nfull) { return static_cast<unsigned>((nfull + kLanes - 1) / kLanes); }
 
-template <class M, typename Sym, int SPP, int kL = kLanes>
+template <class M, typename Sym, int SPP, int kL = kLanes, bool kRes = false>
 void menc(const M& md, const void* syms, const uint8_t* tids, uint64_t L, uint64_t nfull, uint8_t* slots, uint64_t cap,
           uint32_t* lens, uint32_t* st, ChunkInit ini, uint32_t lds, hipStream_t s) {
-    k_menc<M, Sym, SPP, kL><<<static_cast<unsigned>((nfull + kL - 1) / kL), kL, lds, s>>>(
+    k_menc<M, Sym, SPP, kL, kRes><<<static_cast<unsigned>((nfull + kL - 1) / kL), kL, lds, s>>>(
         md, static_cast<const Sym*>(syms), tids, L, nfull, slots, cap, lens, st, ini);
 }
-template <class M, typename Sym, int SPP, int kL = kLanes>
+template <class M, typename Sym, int SPP, int kL = kLanes, bool kRes = false>
 void mdec(const M& md, const uint8_t* in, uint64_t cap, const uint64_t* offs, const uint32_t* lens, const uint8_t* tids,
           uint64_t L, uint64_t nfull, int gen_kind, void* out, uint32_t* st, ChunkInit ini, uint32_t lds, hipStream_t s) {
-    k_mdec<M, Sym, SPP, kL><<<static_cast<unsigned>((nfull + kL - 1) / kL), kL, lds, s>>>(
+    k_mdec<M, Sym, SPP, kL, kRes><<<static_cast<unsigned>((nfull + kL - 1) / kL), kL, lds, s>>>(
         md, in, cap, offs, lens, tids, L, nfull, gen_kind, static_cast<Sym*>(out), st, ini);
 }
 
@@ -47,6 +47,13 @@ struct IndepFast {
 // the full chunks of a fixed-chunk Independent call (ans_codecs_indep_enc.hip / _dec.hip)
 void indep_fast_encode(const IndepFast& f, const void* syms, int w, const uint8_t* tids, uint64_t L, uint64_t nfull,
                        uint8_t* slots, uint64_t cap, uint32_t* lens, uint32_t* st, ChunkInit ini, hipStream_t s);
+// resume (ans_codecs_indep_push.hip, k_menc<kRes>): pushes onto the messages in the slots; a lane
+// whose message is too short for the prologue leaves kResumeExact in lens[c] for the exact kernel
+void indep_fast_push(const IndepFast& f, const void* syms, int w, const uint8_t* tids, uint64_t L, uint64_t nfull,
+                     uint8_t* slots, uint64_t cap, uint32_t* lens, uint32_t* st, hipStream_t s);
+// (ans_codecs_indep_pop.hip, k_mdec<kRes>): pops from the messages in the slots, in place; lens in/out
+void indep_fast_pop(const IndepFast& f, uint8_t* slots, uint64_t cap, uint32_t* lens, const uint8_t* tids, uint64_t L,
+                    uint64_t nfull, void* out, int w, uint32_t* st, hipStream_t s);
 void indep_fast_decode(const IndepFast& f, const uint8_t* in, uint64_t cap, const uint64_t* offs, const uint32_t* lens,
                        const uint8_t* tids, uint64_t L, uint64_t nfull, int gen_kind, void* out, int w, uint32_t* st,
                        ChunkInit ini, hipStream_t s);

@@ -84,6 +84,60 @@ def device_case(gpu, codec, syms_np, L, w, tids_np=None, stream=None):
     return te, td, comp
 
 
+def resume_case(gpu, ts, d_syms, d_tids, L, h, stream):
+    """Resume (ans_dev_independent_push / _pop) against the one-call encode / decode of the same u8
+    symbols, in this process: the two-call push is encode of X[:, h:] then push of X[:, :h] onto it
+    (the same bytes as encode of X); the pop takes X[:, :h] back off encode(X) and the rest is
+    decoded from what remains."""
+    torch.cuda.set_stream(stream)
+    n = len(d_syms)
+    nch = n // L
+    heads, tails = (d_syms.view(nch, L)[:, :h].contiguous().view(-1), d_syms.view(nch, L)[:, h:].contiguous().view(-1))
+    htid, ttid = (d_tids.view(nch, L)[:, :h].contiguous().view(-1), d_tids.view(nch, L)[:, h:].contiguous().view(-1))
+    cap1, cap = ts.slot_capacity(L), ts.slot_capacity(L - h) + ts.slot_capacity(h)
+    ref = torch.empty(nch * cap1, dtype=torch.uint8, device="cuda")
+    ref_lens = torch.zeros(nch, dtype=torch.int32, device="cuda")
+    slots = torch.empty(nch * cap, dtype=torch.uint8, device="cuda")
+    lens = torch.zeros(nch, dtype=torch.int32, device="cuda")
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    out, out_h, out_t = torch.empty_like(d_syms), torch.empty_like(heads), torch.empty_like(tails)
+    reps, warm = 5, 2
+    names = ["encode", "decode", "encode_tails", "push_heads", "pop_heads", "decode_tails"]
+    steps = [lambda: ts.dev_encode(d_tids, d_syms, 1, n, L, ref, cap1, ref_lens, status, stream),
+             lambda: ts.dev_decode(d_tids, ref, None, cap1, ref_lens, n, L, out, 1, status, stream),
+             lambda: ts.dev_encode(ttid, tails, 1, len(tails), L - h, slots, cap, lens, status, stream),
+             lambda: ts.dev_push(htid, heads, 1, len(heads), h, slots, cap, lens, status, stream),
+             lambda: ts.dev_pop(htid, slots, cap, lens, len(heads), h, out_h, 1, status, stream),
+             lambda: ts.dev_decode(ttid, slots, None, cap, lens, len(tails), L - h, out_t, 1, status, stream)]
+    ms = np.zeros(len(steps))
+    for r in range(warm + reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(steps) + 1)]
+        ev[0].record(stream)
+        for k, f in enumerate(steps):
+            f()
+            ev[k + 1].record(stream)
+            if r == 0 and k == 3:  # the pushed messages are encode(X)'s
+                assert gpu.status(status, stream) == 0
+                assert torch.equal(lens, ref_lens)
+                a, b = slots.view(nch, cap), ref.view(nch, cap1)
+                for c in (0, nch // 2, nch - 1):
+                    ln = int(lens[c])
+                    assert torch.equal(a[c, :ln], b[c, :ln]), "push bytes"
+        torch.cuda.synchronize()
+        if r >= warm:
+            ms += [ev[k].elapsed_time(ev[k + 1]) for k in range(len(steps))]
+    assert gpu.status(status, stream) == 0
+    assert torch.equal(out, d_syms) and torch.equal(out_h, heads) and torch.equal(out_t, tails), "round trip"
+    t = dict(zip(names, (ms / reps).tolist()))
+    torch.cuda.set_stream(torch.cuda.default_stream())
+    return dict(symbols=n, chunk_len=L, h=h, passes=reps, **{k + "_ms": round(v, 4) for k, v in t.items()},
+                push_two_call_over_one_call=round((t["encode_tails"] + t["push_heads"]) / t["encode"], 3),
+                pop_two_call_over_one_call=round((t["pop_heads"] + t["decode_tails"]) / t["decode"], 3),
+                what="HIP-event means of `passes` passes; push_heads / pop_heads by the kernels the `kernels` field "
+                     "names (fast: k_menc<kRes> / k_mdec<kRes>; exact: k_push64 / k_pop64), encode / decode of the "
+                     "same symbols beside them")
+
+
 def host_case(enc, dec, n, w):
     t0 = time.perf_counter()
     e = enc()
@@ -126,6 +180,7 @@ def main():
             te, td, comp = device_case(g, ts, d_syms, L, 1, d_tids, stream)
             res[f"independent_lanes{lanes}"] = line(n, 1, te, td, comp)
         ts.lanes(0)
+    res["independent_resume"] = resume_case(g, ts, d_syms, d_tids, L, L // 2, stream)
     if li <= 26:
         tids, syms = d_tids.cpu().numpy().astype(np.uint32), d_syms.cpu().numpy()
         res["independent"].update(host_case(lambda: ts.encode_chunks(tids, syms, L),
