@@ -29,6 +29,11 @@ auto with_sym_type(int sym_bytes, F&& f) {
     default: return f(uint32_t{});
     }
 }
+// ... and of a valid_width_u64 width (the 64-bit codecs)
+template <class F>
+auto with_sym_type_u64(int sym_bytes, F&& f) {
+    return sym_bytes == 8 ? f(uint64_t{}) : with_sym_type(sym_bytes, f);
+}
 
 // the lowest error code raised in a status word (bit k = code k)
 inline int lowest_status(uint32_t bits) {

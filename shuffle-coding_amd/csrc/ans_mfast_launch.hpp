@@ -1,15 +1,16 @@
 // ans_mfast_launch.hpp — launchers of the ans_mfast.hpp skeletons, shared by ans_codecs.hip
-// (Uniform, LogUniform) and the Independent<Categorical> units ans_codecs_indep_{enc,dec}.hip,
-// which hold that codec's many instantiations (norm range x renorm screen x symbol width) so
-// they compile in parallel.
+// (Uniform, LogUniform) and the four Independent<Categorical> units
+// ans_codecs_indep_{enc,push,dec,pop}.hip.  Those hold that codec's many instantiations (norm
+// range x renorm screen x lane layout x symbol width, for new and for resumed messages) so they
+// compile in parallel; their one dispatch ladder per side is ans_codecs_indep_impl.hpp.
 #pragma once
+
+#include <type_traits>
 
 #include "ans_mfast.hpp"
 
 namespace shuffle_coding {
 namespace mfast {
-
-inline unsigned mgrid(uint64_t nfull) { return static_cast<unsigned>((nfull + kLanes - 1) / kLanes); }
 
 template <class M, typename Sym, int SPP, int kL = kLanes, bool kRes = false>
 void menc(const M& md, const void* syms, const uint8_t* tids, uint64_t L, uint64_t nfull, uint8_t* slots, uint64_t cap,
@@ -22,6 +23,47 @@ void mdec(const M& md, const uint8_t* in, uint64_t cap, const uint64_t* offs, co
           uint64_t L, uint64_t nfull, int gen_kind, void* out, uint32_t* st, ChunkInit ini, uint32_t lds, hipStream_t s) {
     k_mdec<M, Sym, SPP, kL, kRes><<<static_cast<unsigned>((nfull + kL - 1) / kL), kL, lds, s>>>(
         md, in, cap, offs, lens, tids, L, nfull, gen_kind, static_cast<Sym*>(out), st, ini);
+}
+
+// What a call hands through its dispatch to the launch, where it is unpacked into menc's / mdec's
+// parameters: nfull chunks of L symbols of w bytes (tids: a table id per position, Independent only).
+struct EncArgs {
+    const void* syms;
+    int w;
+    const uint8_t* tids;
+    uint64_t L, nfull;
+    uint8_t* slots;
+    uint64_t cap;
+    uint32_t* lens;
+    uint32_t* st;
+    ChunkInit ini;
+    hipStream_t s;
+};
+struct DecArgs {
+    const uint8_t* in;
+    uint64_t cap;
+    const uint64_t* offs;
+    const uint32_t* lens;
+    const uint8_t* tids;
+    uint64_t L, nfull;
+    int gen_kind;
+    void* out;
+    int w;
+    uint32_t* st;
+    ChunkInit ini;
+    hipStream_t s;
+};
+// the launch of one instantiation: the tag arguments give Sym as a value and SPP as an Spp<N>
+template <int N>
+using Spp = std::integral_constant<int, N>;
+template <class M, int kL = kLanes, bool kRes = false, typename Sym, class P>
+void menc_of(const M& md, const EncArgs& a, uint32_t lds, Sym, P) {
+    menc<M, Sym, P::value, kL, kRes>(md, a.syms, a.tids, a.L, a.nfull, a.slots, a.cap, a.lens, a.st, a.ini, lds, a.s);
+}
+template <class M, int kL = kLanes, bool kRes = false, typename Sym, class P>
+void mdec_of(const M& md, const DecArgs& a, uint32_t lds, Sym, P) {
+    mdec<M, Sym, P::value, kL, kRes>(md, a.in, a.cap, a.offs, a.lens, a.tids, a.L, a.nfull, a.gen_kind, a.out, a.st, a.ini,
+                                     lds, a.s);
 }
 
 // An Independent<Categorical> set's fast-kernel images (built by ans_codecs.hip build_indep_fast).
@@ -45,18 +87,15 @@ struct IndepFast {
 };
 
 // the full chunks of a fixed-chunk Independent call (ans_codecs_indep_enc.hip / _dec.hip)
-void indep_fast_encode(const IndepFast& f, const void* syms, int w, const uint8_t* tids, uint64_t L, uint64_t nfull,
-                       uint8_t* slots, uint64_t cap, uint32_t* lens, uint32_t* st, ChunkInit ini, hipStream_t s);
+void indep_fast_encode(const IndepFast& f, const EncArgs& a);
+void indep_fast_decode(const IndepFast& f, const DecArgs& a);
 // resume (ans_codecs_indep_push.hip, k_menc<kRes>): pushes onto the messages in the slots; a lane
-// whose message is too short for the prologue leaves kResumeExact in lens[c] for the exact kernel
-void indep_fast_push(const IndepFast& f, const void* syms, int w, const uint8_t* tids, uint64_t L, uint64_t nfull,
-                     uint8_t* slots, uint64_t cap, uint32_t* lens, uint32_t* st, hipStream_t s);
-// (ans_codecs_indep_pop.hip, k_mdec<kRes>): pops from the messages in the slots, in place; lens in/out
-void indep_fast_pop(const IndepFast& f, uint8_t* slots, uint64_t cap, uint32_t* lens, const uint8_t* tids, uint64_t L,
-                    uint64_t nfull, void* out, int w, uint32_t* st, hipStream_t s);
-void indep_fast_decode(const IndepFast& f, const uint8_t* in, uint64_t cap, const uint64_t* offs, const uint32_t* lens,
-                       const uint8_t* tids, uint64_t L, uint64_t nfull, int gen_kind, void* out, int w, uint32_t* st,
-                       ChunkInit ini, hipStream_t s);
+// whose message is too short for the prologue leaves kResumeExact in lens[c] for the exact kernel;
+// a.ini is ChunkInit{}
+void indep_fast_push(const IndepFast& f, const EncArgs& a);
+// (ans_codecs_indep_pop.hip, k_mdec<kRes>): pops from the messages in the slots a.in, in place;
+// a.lens in/out, a.offs NULL, a.gen_kind ANS_GEN_EMPTY, a.ini ChunkInit{}
+void indep_fast_pop(const IndepFast& f, const DecArgs& a);
 
 }  // namespace mfast
 }  // namespace shuffle_coding

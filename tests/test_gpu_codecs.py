@@ -130,6 +130,83 @@ def test_independent_bit_exact(gpu, chunk_len):
     assert e.value.code == A.ANS_E_SYMBOL
 
 
+def _container(msgs):
+    lens = np.array([len(m) for m in msgs], np.uint64)
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+    return np.frombuffer(b"".join(msgs), np.uint8).copy(), offsets, lens
+
+
+def _messages(data, offsets, lens):
+    return [bytes(data[int(o):int(o) + int(n)]) for o, n in zip(offsets, lens)]
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint32])
+def test_independent_more_than_256_tables(gpu, dtype):
+    """257 tables, one past the one-byte table id: the ids reach the device as u32 (the exact
+    kernels' md.tid).  Host fixed and variable chunks and the resume pair equal the oracle byte for
+    byte; an id outside the set is ANS_E_ARG from every entry."""
+    rng = np.random.default_rng(257)
+    tables = [rng.integers(1, 8, size=int(k)).astype(np.uint64) for k in rng.integers(2, 5, size=257)]
+    L, h, nfull, ragged = 33, 20, 9, 5
+    n = nfull * L + ragged
+    tids = rng.integers(0, 257, size=n).astype(np.uint32)
+    tids[[0, L, n - 1]] = 256
+    syms = np.array([rng.integers(0, len(tables[t])) for t in tids], np.uint64)
+    ts = A.GpuTableSet(gpu, [A.Categorical(m) for m in tables])
+
+    def oenc(s, t, chunk_len, kind, seed):
+        return orc.codec_encode_chunks(orc.CODEC_INDEPENDENT, s, chunk_len, tables=tables, tids=t, kind=kind, seed=seed)
+
+    starts = np.array([0, 1, 40, 40, 41, 150, n], np.uint64)  # uneven, one empty chunk
+    full = np.arange(nfull * L).reshape(nfull, L)
+    hi = np.concatenate([full[:, :h].reshape(-1), np.arange(nfull * L, n)])  # heads; the ragged chunk whole
+    ti = full[:, h:].reshape(-1)
+    for kind, seed in [(A.GEN_ZEROS, 0), (A.GEN_RANDOM, 3)]:
+        # fixed chunks
+        _check(lambda s, cl, k, sd: ts.encode_chunks(tids, s, cl, k, sd),
+               lambda d, o, ln, n_, cl, dt, k, sd: ts.decode_chunks(tids, d, o, ln, cl, dt, k, sd),
+               lambda s, cl, k, sd: oenc(s, tids, cl, k, sd),
+               lambda d, o, ln, n_, cl, k, sd: orc.codec_decode_chunks(orc.CODEC_INDEPENDENT, d, o, ln, n_, cl,
+                                                                       tables=tables, tids=tids, kind=k, seed=sd),
+               syms, L, dtype, kind, seed)
+        # variable chunks: chunk c is the oracle's one-chunk encode from initial message seed + c
+        vd, vo, vl = ts.encode_var_chunks(tids, syms.astype(dtype), starts, kind, seed)
+        for c in range(len(starts) - 1):
+            a, b = int(starts[c]), int(starts[c + 1])
+            if b == a:
+                want = (orc.Message.random(seed + c) if kind == A.GEN_RANDOM else orc.Message.zeros()).flatten()
+            else:
+                want = oenc(syms[a:b], tids[a:b], b - a, kind, seed + c)[0].tobytes()
+            assert vd[int(vo[c]):int(vo[c]) + int(vl[c])].tobytes() == bytes(want), c
+        assert np.array_equal(ts.decode_var_chunks(tids, vd, vo, vl, starts, dtype, kind, seed), syms.astype(dtype))
+        # resume: the heads pushed onto the encoded tails are the one-shot encode of the whole, and
+        # popping them off the whole leaves the tails
+        od, oo, ol = oenc(syms, tids, L, kind, seed)
+        td, to, tl = ts.encode_chunks(tids[ti], syms[ti].astype(dtype), L - h, kind, seed)
+        last = orc.Message.random(seed + nfull) if kind == A.GEN_RANDOM else orc.Message.zeros()
+        tails = _messages(td, to, tl) + [bytes(last.flatten())]
+        pd, po, pl = ts.push_chunks(tids[hi], syms[hi].astype(dtype), h, *_container(tails))
+        assert np.array_equal(pl, ol) and np.array_equal(po, oo)
+        assert pd.tobytes() == od.tobytes()
+        back, (rd, ro, rl) = ts.pop_chunks(tids[hi], od, oo, ol, h, dtype)
+        assert np.array_equal(back, syms[hi].astype(dtype))
+        assert _messages(rd, ro, rl) == tails
+    # an id outside the set, first, in the middle or last
+    s = syms.astype(dtype)
+    for k in (0, n // 2, n - 1):
+        bad = tids.copy()
+        bad[k] = 257
+        for call in (lambda: ts.encode_chunks(bad, s, L),
+                     lambda: ts.decode_chunks(bad, od, oo, ol, L, dtype),
+                     lambda: ts.encode_var_chunks(bad, s, starts),
+                     lambda: ts.decode_var_chunks(bad, vd, vo, vl, starts, dtype),
+                     lambda: ts.push_chunks(bad[hi], s[hi], h, *_container(tails)),
+                     lambda: ts.pop_chunks(bad[hi], od, oo, ol, h, dtype)):
+            with pytest.raises(A.AnsError) as e:
+                call()
+            assert e.value.code == A.ANS_E_ARG
+
+
 @pytest.mark.parametrize("which", ["norm_2^45", "nsym_100000"])
 def test_wide_categorical_through_the_table_api(gpu, which):
     """Categoricals the u32 table kernels do not take run on the exact 64-bit kernels through
