@@ -152,6 +152,23 @@ void ans_gpu_table_free(ans_gpu_table *gt);
 #define ANS_PATH_ENC_SHIFT 512u /* packed large-alphabet encoder whose renorm reads a shift byte per
                                   * mass (every mass <= 4096) instead of comparing bit lengths */
 int ans_gpu_table_paths(const ans_gpu_table *gt, uint32_t *paths);
+/* Which coder kernels the context's last launcher call started, in launch order, each with every
+ * template argument its launch ladder chose, as text joined by ';':
+ *   k_encode<u8,kmax=2,k32=0,grows=0,var=0,nr=std,m24=1>;k_encode_generic<u8,lds=1,fast=1>
+ *   k_decode<u8,spp=16,mode=u,p24=1,j4=0,var=0,nr=std>      (mode: far / rows / u; nr: std / small / big)
+ *   k_encode_w<u16,k32=1,pack=1,sa=1,var=0,nr=std>   k_decode_w<u16,compact=1,prefix=0,var=0,p24=1,nr=std>
+ *   k_decode_g<u16,nr=std>   k_decode_generic<u8,lds=1,fast=1>
+ *   k_menc<indep,u8,spp=16,lanes=256,res=0,rare=0,nr=std>   k_mdec<indep,u8,spp=16,lanes=256,res=0,lean=1,nr=std>
+ *   k_encode64<catset,u8>   k_decode64<catset,u8>   k_push64<u8>   k_pop64<u8>
+ * The calls that write it are the Categorical table's (sections 3 and 4: fixed, ragged and variable
+ * chunks, host or device buffers; a pipelined host call leaves its last batch's launches) and the
+ * Independent ones (new messages and resume); helper kernels (staging, compaction) are not named,
+ * and the other calls (and calls that return before any launch: no symbols, bad arguments) leave
+ * the record as it was.  Empty before the first such call.
+ * Writes *len = the text's bytes (without the terminating NUL) and, if cap > *len, the
+ * NUL-terminated text into buf; a shorter buf (or buf == NULL) is ANS_E_LEN with *len set.
+ * For tests and tuning: the text is not a stable interface. */
+int ans_gpu_last_launch(const ans_gpu *g, char *buf, size_t cap, size_t *len);
 /* worst-case stream bytes of one chunk of chunk_len symbols, rounded up to 16 */
 int ans_gpu_slot_capacity(const ans_gpu_table *gt, uint64_t chunk_len, uint64_t *slot_cap);
 

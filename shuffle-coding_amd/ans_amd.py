@@ -76,6 +76,7 @@ SIGNATURES = {
     "ans_gpu_free": (None, [vp]),
     "ans_gpu_set_batch_bytes": (ci, [vp, u64]),
     "ans_gpu_pipe_depth": (ci, [vp, ctypes.POINTER(ci)]),
+    "ans_gpu_last_launch": (ci, [vp, ctypes.c_char_p, sz, ctypes.POINTER(sz)]),
     "ans_host_alloc": (ci, [sz, ctypes.POINTER(vp)]),
     "ans_host_free": (None, [vp]),
     "ans_gpu_table_create": (ci, [vp, vp, ctypes.POINTER(vp)]),
@@ -610,6 +611,17 @@ class Gpu:
         d = ci(0)
         _check(lib().ans_gpu_pipe_depth(self.h, ctypes.byref(d)), "ans_gpu_pipe_depth")
         return d.value
+
+    def last_launch(self):
+        """The coder kernels this context's last table or Independent call started, in launch
+        order, with their template arguments (ans_gpu_last_launch): 'k_encode<u8,kmax=2,...>;...'."""
+        n = sz(0)
+        rc = lib().ans_gpu_last_launch(self.h, None, 0, ctypes.byref(n))
+        if rc != ANS_E_LEN:
+            _check(rc, "ans_gpu_last_launch")
+        buf = ctypes.create_string_buffer(n.value + 1)
+        _check(lib().ans_gpu_last_launch(self.h, buf, n.value + 1, ctypes.byref(n)), "ans_gpu_last_launch")
+        return buf.value.decode("ascii")
 
     def status(self, d_status, stream=None):
         st = ci(0)

@@ -10,6 +10,7 @@
 #include <stdexcept>
 
 #include "ans_fast.hpp"
+#include "ans_launchlog.hpp"
 #include "ans_table.hpp"
 
 using namespace shuffle_coding;
@@ -56,6 +57,7 @@ struct ans_gpu {
     uint64_t batch_bytes;  // symbol bytes per pipeline batch (0 = default)
     void* d_scratch;       // device scratch of the device-resident graph calls (ans_graph.hip)
     size_t cap_scratch;
+    LaunchLog last;  // the last launcher call's coder kernels (ans_gpu_last_launch)
 };
 
 struct ans_gpu_table {

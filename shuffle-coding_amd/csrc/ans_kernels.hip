@@ -1230,7 +1230,7 @@ int ans_gpu_create(int device, ans_gpu** out) try {
     HIP_TRY(hipSetDevice(device));
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) ncu = 256;
-    auto* g = new (std::nothrow) ans_gpu{device, ncu, nullptr, nullptr, 0, nullptr, 0};
+    auto* g = new (std::nothrow) ans_gpu{device, ncu, nullptr, nullptr, 0, nullptr, 0, LaunchLog{}};
     if (!g) return ANS_E_ALLOC;
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
         delete g;
@@ -1263,6 +1263,53 @@ int ans_gpu_set_batch_bytes(ans_gpu* g, uint64_t batch_bytes) try {
 int ans_gpu_pipe_depth(const ans_gpu* g, int* depth) try {
     if (!g || !depth) return ANS_E_ARG;
     *depth = g->pipe ? g->pipe->depth : 0;
+    return ANS_OK;
+} ANS_CATCH
+
+// The launch record as text (include/ans_capi.h).  Formatting happens here, never on a launch path.
+int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) try {
+    if (!g || !len) return ANS_E_ARG;
+    static const char* const kSym[9] = {"?", "u8", "u16", "?", "u32", "?", "?", "?", "u64"};
+    static const char* const kNr[3] = {"std", "small", "big"};    // fast::kNormStd / kNormSmall / kNormBig
+    static const char* const kMode[3] = {"far", "rows", "u"};     // fast::kModeFar / kModeRows / kModeU
+    static_assert(fast::kNormStd == 0 && fast::kNormSmall == 1 && fast::kNormBig == 2, "kNr's order");
+    static_assert(fast::kModeFar == 0 && fast::kModeRows == 1 && fast::kModeU == 2, "kMode's order");
+    const LaunchLog& log = g->last;
+    char text[LaunchLog::kCap * 96 + 8];
+    size_t at = 0;
+    const uint32_t n = std::min(log.n, LaunchLog::kCap);
+    for (uint32_t i = 0; i < n; ++i) {
+        const LaunchRec& r = log.r[i];
+        const char* sym = kSym[r.sym_bytes <= 8 ? r.sym_bytes : 0];
+        const int16_t* a = r.a;
+        auto nr = [&](int v) { return kNr[v >= 0 && v < 3 ? v : 0]; };
+        char* o = text + at;
+        const size_t room = sizeof(text) - at;
+        int w = 0;
+        if (i) { *o++ = ';'; ++at; }
+        switch (r.kind) {
+        case kRecEncode: w = std::snprintf(o, room - 1, "k_encode<%s,kmax=%d,k32=%d,grows=%d,var=%d,nr=%s,m24=%d>", sym, a[0], a[1], a[2], a[3], nr(a[4]), a[5]); break;
+        case kRecEncodeW: w = std::snprintf(o, room - 1, "k_encode_w<%s,k32=%d,pack=%d,sa=%d,var=%d,nr=%s>", sym, a[0], a[1], a[2], a[3], nr(a[4])); break;
+        case kRecDecode: w = std::snprintf(o, room - 1, "k_decode<%s,spp=%d,mode=%s,p24=%d,j4=%d,var=%d,nr=%s>", sym, a[0], kMode[a[1] >= 0 && a[1] < 3 ? a[1] : 0], a[2], a[3], a[4], nr(a[5])); break;
+        case kRecDecodeW: w = std::snprintf(o, room - 1, "k_decode_w<%s,compact=%d,prefix=%d,var=%d,p24=%d,nr=%s>", sym, a[0], a[1], a[2], a[3], nr(a[4])); break;
+        case kRecDecodeG: w = std::snprintf(o, room - 1, "k_decode_g<%s,nr=%s>", sym, nr(a[0])); break;
+        case kRecEncodeGeneric: w = std::snprintf(o, room - 1, "k_encode_generic<%s,lds=%d,fast=%d>", sym, a[0], a[1]); break;
+        case kRecDecodeGeneric: w = std::snprintf(o, room - 1, "k_decode_generic<%s,lds=%d,fast=%d>", sym, a[0], a[1]); break;
+        case kRecMenc: w = std::snprintf(o, room - 1, "k_menc<indep,%s,spp=%d,lanes=%d,res=%d,rare=%d,nr=%s>", sym, a[0], a[1], a[2], a[3], nr(a[4])); break;
+        case kRecMdec: w = std::snprintf(o, room - 1, "k_mdec<indep,%s,spp=%d,lanes=%d,res=%d,lean=%d,nr=%s>", sym, a[0], a[1], a[2], a[3], nr(a[4])); break;
+        case kRecEncode64: w = std::snprintf(o, room - 1, "k_encode64<catset,%s>", sym); break;
+        case kRecDecode64: w = std::snprintf(o, room - 1, "k_decode64<catset,%s>", sym); break;
+        case kRecPush64: w = std::snprintf(o, room - 1, "k_push64<%s>", sym); break;
+        case kRecPop64: w = std::snprintf(o, room - 1, "k_pop64<%s>", sym); break;
+        default: w = std::snprintf(o, room - 1, "?"); break;
+        }
+        at += static_cast<size_t>(w);
+    }
+    if (log.n > LaunchLog::kCap) at += static_cast<size_t>(std::snprintf(text + at, sizeof(text) - at, ";+%u", log.n - LaunchLog::kCap));
+    *len = at;
+    if (!buf || cap <= at) return ANS_E_LEN;
+    std::memcpy(buf, text, at);
+    buf[at] = 0;
     return ANS_OK;
 } ANS_CATCH
 

@@ -8,6 +8,21 @@
 
 namespace {
 
+// A coder kernel's launch: LAUNCH_X(log, template arguments...)<<<grid, block, lds, stream>>>(...)
+// adds the record entry (ans_launchlog.hpp LaunchLog) and names the kernel from one argument list, so
+// the record of ans_gpu_last_launch cannot name another instantiation than the one started.
+#define LAUNCH_ENCODE(LOG, KM, K32, G, VAR, NR, M24) \
+    (LOG).add(kRecEncode, sizeof(Sym), KM, K32, G, VAR, NR, M24), fast::k_encode<Sym, KM, K32, G, VAR, NR, M24>
+#define LAUNCH_ENCODE_W(LOG, K32, PK, SA, VAR, NR) \
+    (LOG).add(kRecEncodeW, sizeof(Sym), K32, PK, SA, VAR, NR), fast::k_encode_w<Sym, K32, PK, SA, VAR, NR>
+#define LAUNCH_DECODE(LOG, SPP, MODE, P24, J4, VAR, NR) \
+    (LOG).add(kRecDecode, sizeof(Sym), SPP, MODE, P24, J4, VAR, NR), fast::k_decode<Sym, SPP, MODE, P24, J4, VAR, NR>
+#define LAUNCH_DECODE_W(LOG, COMPACT, PREFIX, VAR, P24, NR) \
+    (LOG).add(kRecDecodeW, sizeof(Sym), COMPACT, PREFIX, VAR, P24, NR), fast::k_decode_w<Sym, COMPACT, PREFIX, VAR, P24, NR>
+#define LAUNCH_DECODE_G(LOG, NR) (LOG).add(kRecDecodeG, sizeof(Sym), NR), fast::k_decode_g<Sym, NR>
+#define LAUNCH_ENCODE_GENERIC(LOG, LDS, FAST) (LOG).add(kRecEncodeGeneric, sizeof(Sym), LDS, FAST), k_encode<Sym, LDS, FAST>
+#define LAUNCH_DECODE_GENERIC(LOG, LDS, FAST) (LOG).add(kRecDecodeGeneric, sizeof(Sym), LDS, FAST), k_decode<Sym, LDS, FAST>
+
 // ------------------------------------------------------------------ kernels
 
 // Encode: lane = chunk; symbols consumed last -> first (IID::push, src/codec.rs:417).
@@ -341,6 +356,7 @@ int launch_staged_encode(ans_gpu_table* gt, const Sym* syms, ChunkSpan<Sym> span
     {
         if (!staged_encode_ok<Sym>(gt) || nchunks == 0) return kNotStaged;
         const FastTable& ft = gt->ft;
+        LaunchLog& log = gt->g->last;
         constexpr uint64_t GS = 128 / sizeof(Sym);
         const uint64_t lpad = std::max<uint64_t>(GS, (lmax + GS - 1) / GS * GS);
         void* mem = nullptr;
@@ -361,7 +377,7 @@ int launch_staged_encode(ans_gpu_table* gt, const Sym* syms, ChunkSpan<Sym> span
         if constexpr (sizeof(Sym) > 1) wide = ft.enc_wide;
         if (wide) {
             if constexpr (sizeof(Sym) > 1) {
-#define ENCV2(K32, PK, SA, NR) fast::k_encode_w<Sym, K32, PK, SA, true, NR><<<grid, fast::kBlock, wlds, s>>>(ft, stage, lpad, nchunks, d_slots, slot_cap, d_lens, d_status, ini, vlen)
+#define ENCV2(K32, PK, SA, NR) LAUNCH_ENCODE_W(log, K32, PK, SA, true, NR)<<<grid, fast::kBlock, wlds, s>>>(ft, stage, lpad, nchunks, d_slots, slot_cap, d_lens, d_status, ini, vlen)
 #define ENCV(K32, NR) if (ft.enc_sa) ENCV2(K32, true, true, NR); else if (ft.enc_pack) ENCV2(K32, true, false, NR); else ENCV2(K32, false, false, NR)
             if (ft.nr == fast::kNormBig) ENCV(true, fast::kNormBig);  // (K < 2^25)
             else if (k32) ENCV(true, fast::kNormStd);
@@ -370,7 +386,7 @@ int launch_staged_encode(ans_gpu_table* gt, const Sym* syms, ChunkSpan<Sym> span
 #undef ENCV2
             }
         } else {  // LDS rows (ans_fast.hpp k_encode, kVar)
-#define ENCL(KM, K32, NR) fast::k_encode<Sym, KM, K32, false, true, NR><<<grid, fast::kBlock, fast::kEncSharedBytes, s>>>(ft, stage, lpad, nchunks, d_slots, slot_cap, d_lens, d_status, ini, vlen)
+#define ENCL(KM, K32, NR) LAUNCH_ENCODE(log, KM, K32, false, true, NR, false)<<<grid, fast::kBlock, fast::kEncSharedBytes, s>>>(ft, stage, lpad, nchunks, d_slots, slot_cap, d_lens, d_status, ini, vlen)
             if (ft.nr == fast::kNormSmall) {  // (kmax <= 2, K >= 2^40)
                 ENCL(2, false, fast::kNormSmall);
             } else if (ft.nr == fast::kNormBig) {  // (K < 2^25)
@@ -449,6 +465,7 @@ int launch_staged_decode(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t*
     {
         if (!staged_decode_ok<Sym>(gt) || nchunks == 0 || lmax > (1ull << 24)) return kNotStaged;
         const FastTable& ft = gt->ft;
+        LaunchLog& log = gt->g->last;
         constexpr uint64_t GS = 128 / sizeof(Sym);
         const uint64_t lpad = std::max<uint64_t>(GS, (lmax + GS - 1) / GS * GS);
         void* mem = nullptr;
@@ -471,16 +488,16 @@ int launch_staged_decode(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t*
                 if (ft.dec_c) {
                     FastTable fw = ft;
                     const size_t wl = wide_dec_lds(fw, wgrid, gt->g->ncu);
-                    fast::k_decode_w<Sym, true, false, true, false, NR><<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, lpad, nchunks, gen_kind, stage, d_status, ini, vlen);
+                    LAUNCH_DECODE_W(log, true, false, true, false, NR)<<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, lpad, nchunks, gen_kind, stage, d_status, ini, vlen);
                 } else {
-                    fast::k_decode_w<Sym, false, true, true, false, NR><<<wgrid, fast::kWideDecLanes, 160 * 1024, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, lpad, nchunks, gen_kind, stage, d_status, ini, vlen);
+                    LAUNCH_DECODE_W(log, false, true, true, false, NR)<<<wgrid, fast::kWideDecLanes, 160 * 1024, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, lpad, nchunks, gen_kind, stage, d_status, ini, vlen);
                 }
             });
           }
         } else {  // LDS buckets (ans_fast.hpp k_decode, kVar)
             const size_t lds = fast::kDecTableBytes + fast::kDecRingBytes;
             const unsigned dgrid = static_cast<unsigned>((nchunks + fast::kDecBlock - 1) / fast::kDecBlock);
-#define DEC(SPP, MODE, P24, J4, NR) fast::k_decode<Sym, SPP, MODE, P24, J4, true, NR><<<dgrid, fast::kDecBlock, lds, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, lpad, nchunks, gen_kind, stage, d_status, ini, vlen)
+#define DEC(SPP, MODE, P24, J4, NR) LAUNCH_DECODE(log, SPP, MODE, P24, J4, true, NR)<<<dgrid, fast::kDecBlock, lds, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, lpad, nchunks, gen_kind, stage, d_status, ini, vlen)
             launch_lds_decode<Sym>(ft, [&](auto spp, auto mode, auto p24, auto j4, auto nr) {
                 DEC(decltype(spp)::value, decltype(mode)::value, decltype(p24)::value, decltype(j4)::value, decltype(nr)::value);
             });
@@ -517,6 +534,8 @@ template <typename Sym>
 int launch_encode(ans_gpu_table* gt, const void* d_syms, uint64_t n, uint64_t chunk_len, uint8_t* d_slots,
                   uint64_t slot_cap, uint32_t* d_lens, uint32_t* d_status, hipStream_t s, fast::ChunkInit ini) {
     const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
+    LaunchLog& log = gt->g->last;
+    log.clear();
     if (nchunks == 0) return ANS_OK;
     const DevTable& t = gt->t;
     const Sym* syms = static_cast<const Sym*>(d_syms);
@@ -535,12 +554,12 @@ int launch_encode(ans_gpu_table* gt, const void* d_syms, uint64_t n, uint64_t ch
         const size_t lds = fast::kEncSharedBytes;  // rows (LDS-row kernels) + ring
         const bool k32 = ft.K < (1ull << 32);
         const bool m24 = ft.pmax < (1u << 24);  // (k_encode kM24: the mass word's top byte is free)
-#define ENC(KM, K32, G) do { if (!(G) && m24) fast::k_encode<Sym, KM, K32, false, false, fast::kNormStd, true><<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini); \
-                             else fast::k_encode<Sym, KM, K32, G><<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini); } while (0)
-#define ENCN(KM, K32, NR) fast::k_encode<Sym, KM, K32, false, false, NR><<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini)
+#define ENC(KM, K32, G) do { if (!(G) && m24) LAUNCH_ENCODE(log, KM, K32, false, false, fast::kNormStd, true)<<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini); \
+                             else LAUNCH_ENCODE(log, KM, K32, G, false, fast::kNormStd, false)<<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini); } while (0)
+#define ENCN(KM, K32, NR) LAUNCH_ENCODE(log, KM, K32, false, false, NR, false)<<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini)
 #define ENC_KMAX(G)                                                   \
         if (ft.nr == fast::kNormSmall) {  /* (kmax <= 2, K >= 2^40) */ \
-            fast::k_encode<Sym, 2, false, G, false, fast::kNormSmall><<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini); \
+            LAUNCH_ENCODE(log, 2, false, G, false, fast::kNormSmall, false)<<<grid, fast::kBlock, lds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini); \
         } else if (!(G) && ft.nr == fast::kNormBig) {                 \
             switch (ft.kmax) {                                        \
             case 1: case 2: ENCN(2, true, fast::kNormBig); break;     \
@@ -557,7 +576,7 @@ int launch_encode(ans_gpu_table* gt, const void* d_syms, uint64_t n, uint64_t ch
         if constexpr (sizeof(Sym) > 1) {
             if (ft.enc_wide && (chunk_len * sizeof(Sym)) % 128 == 0) {
                 const size_t wlds = wide_enc_lds(ft);
-#define ENCW2(K32, PK, SA, NR) fast::k_encode_w<Sym, K32, PK, SA, false, NR><<<grid, fast::kBlock, wlds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini)
+#define ENCW2(K32, PK, SA, NR) LAUNCH_ENCODE_W(log, K32, PK, SA, false, NR)<<<grid, fast::kBlock, wlds, s>>>(ft, syms, chunk_len, nfull, d_slots, slot_cap, d_lens, d_status, ini)
 #define ENCW(K32, NR) if (ft.enc_sa) ENCW2(K32, true, true, NR); else if (ft.enc_pack) ENCW2(K32, true, false, NR); else ENCW2(K32, false, false, NR)
                 if (ft.nr == fast::kNormBig) ENCW(true, fast::kNormBig);  // (K < 2^25)
                 else if (k32) ENCW(true, fast::kNormStd);
@@ -581,13 +600,13 @@ int launch_encode(ans_gpu_table* gt, const void* d_syms, uint64_t n, uint64_t ch
     const unsigned grid = grid_for(nchunks - nfull);
     const size_t lds = gt->lds_bytes ? sizeof(DevSym) * (t.nsym + 1) : 0;
     if (gt->lds_bytes && t.fast)
-        k_encode<Sym, true, true><<<grid, kBlock, lds, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, true, true)<<<grid, kBlock, lds, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     else if (gt->lds_bytes)
-        k_encode<Sym, true, false><<<grid, kBlock, lds, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, true, false)<<<grid, kBlock, lds, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     else if (t.fast)
-        k_encode<Sym, false, true><<<grid, kBlock, 0, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, false, true)<<<grid, kBlock, 0, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     else
-        k_encode<Sym, false, false><<<grid, kBlock, 0, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, false, false)<<<grid, kBlock, 0, s>>>(t, syms, n, chunk_len, nullptr, nfull, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     HIP_TRY(hipGetLastError());
     return ANS_OK;
 }
@@ -597,6 +616,8 @@ int launch_decode(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_offs
                   const uint32_t* d_lens, uint64_t n, uint64_t chunk_len, int gen_kind, void* d_syms,
                   uint32_t* d_status, hipStream_t s, fast::ChunkInit ini) {
     const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
+    LaunchLog& log = gt->g->last;
+    log.clear();
     if (nchunks == 0) return ANS_OK;
     const DevTable& t = gt->t;
     const FastTable& ft = gt->ft;
@@ -629,23 +650,23 @@ int launch_decode(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_offs
                         const size_t wl = wide_dec_lds(fw, wgrid, gt->g->ncu);
                         if constexpr (NR == fast::kNormStd) {
                             if (ft.p24)
-                                fast::k_decode_w<Sym, true, false, false, true><<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
+                                LAUNCH_DECODE_W(log, true, false, false, true, fast::kNormStd)<<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
                             else
-                                fast::k_decode_w<Sym, true, false><<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
+                                LAUNCH_DECODE_W(log, true, false, false, false, fast::kNormStd)<<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
                         } else {
-                            fast::k_decode_w<Sym, true, false, false, false, NR><<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
+                            LAUNCH_DECODE_W(log, true, false, false, false, NR)<<<wgrid, fast::kWideDecLanes, wl, s>>>(fw, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
                         }
                     } else if (ft.dec_wide && (chunk_len * sizeof(Sym)) % 64 == 0) {
-                        fast::k_decode_w<Sym, false, true, false, false, NR><<<wgrid, fast::kWideDecLanes, 160 * 1024, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
+                        LAUNCH_DECODE_W(log, false, true, false, false, NR)<<<wgrid, fast::kWideDecLanes, 160 * 1024, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
                     } else {
-                        fast::k_decode_g<Sym, NR><<<grid, fast::kBlock, fast::kDecGRingBytes, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
+                        LAUNCH_DECODE_G(log, NR)<<<grid, fast::kBlock, fast::kDecGRingBytes, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini);
                     }
                 });
             }
         } else {
             const size_t lds = fast::kDecTableBytes + fast::kDecRingBytes;
             const unsigned dgrid = static_cast<unsigned>((nfull + fast::kDecBlock - 1) / fast::kDecBlock);
-#define DEC(SPP, MODE, P24, J4, NR) fast::k_decode<Sym, SPP, MODE, P24, J4, false, NR><<<dgrid, fast::kDecBlock, lds, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini)
+#define DEC(SPP, MODE, P24, J4, NR) LAUNCH_DECODE(log, SPP, MODE, P24, J4, false, NR)<<<dgrid, fast::kDecBlock, lds, s>>>(ft, d_in, slot_cap, d_offsets, d_lens, chunk_len, nfull, gen_kind, out, d_status, ini)
             launch_lds_decode<Sym>(ft, [&](auto spp, auto mode, auto p24, auto j4, auto nr) {
                 DEC(decltype(spp)::value, decltype(mode)::value, decltype(p24)::value, decltype(j4)::value, decltype(nr)::value);
             });
@@ -657,13 +678,13 @@ int launch_decode(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_offs
     const unsigned grid = grid_for(nchunks - nfull);
     const size_t lds = gt->lds_bytes;
     if (gt->lds_bytes && t.fast)
-        k_decode<Sym, true, true><<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, true, true)<<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
     else if (gt->lds_bytes)
-        k_decode<Sym, true, false><<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, true, false)<<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
     else if (t.fast)
-        k_decode<Sym, false, true><<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, false, true)<<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
     else
-        k_decode<Sym, false, false><<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, false, false)<<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, n, chunk_len, nullptr, nfull, nchunks, gen_kind, out, d_status, ini);
     HIP_TRY(hipGetLastError());
     return ANS_OK;
 }
@@ -687,6 +708,8 @@ template <typename Sym>
 int launch_encode_var(ans_gpu_table* gt, const void* d_syms, uint64_t nchunks, const uint64_t* d_starts,
                       uint8_t* d_slots, uint64_t slot_cap, uint32_t* d_lens, uint32_t* d_status, hipStream_t s,
                       fast::ChunkInit ini, uint64_t lmax) {
+    LaunchLog& log = gt->g->last;
+    log.clear();
     if (nchunks == 0) return ANS_OK;
     const DevTable& t = gt->t;
     const Sym* syms = static_cast<const Sym*>(d_syms);
@@ -698,13 +721,13 @@ int launch_encode_var(ans_gpu_table* gt, const void* d_syms, uint64_t nchunks, c
     const unsigned grid = grid_for(nchunks);
     const size_t lds = gt->lds_bytes ? sizeof(DevSym) * (t.nsym + 1) : 0;
     if (gt->lds_bytes && t.fast)
-        k_encode<Sym, true, true><<<grid, kBlock, lds, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, true, true)<<<grid, kBlock, lds, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     else if (gt->lds_bytes)
-        k_encode<Sym, true, false><<<grid, kBlock, lds, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, true, false)<<<grid, kBlock, lds, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     else if (t.fast)
-        k_encode<Sym, false, true><<<grid, kBlock, 0, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, false, true)<<<grid, kBlock, 0, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     else
-        k_encode<Sym, false, false><<<grid, kBlock, 0, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
+        LAUNCH_ENCODE_GENERIC(log, false, false)<<<grid, kBlock, 0, s>>>(t, syms, 0, 0, d_starts, 0, nchunks, d_slots, slot_cap, d_lens, d_status, ini);
     HIP_TRY(hipGetLastError());
     return ANS_OK;
 }
@@ -713,6 +736,8 @@ template <typename Sym>
 int launch_decode_var(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_offsets, uint64_t slot_cap,
                       const uint32_t* d_lens, uint64_t nchunks, const uint64_t* d_starts, int gen_kind, void* d_syms,
                       uint32_t* d_status, hipStream_t s, fast::ChunkInit ini, uint64_t lmax) {
+    LaunchLog& log = gt->g->last;
+    log.clear();
     if (nchunks == 0) return ANS_OK;
     const DevTable& t = gt->t;
     Sym* out = static_cast<Sym*>(d_syms);
@@ -724,13 +749,13 @@ int launch_decode_var(ans_gpu_table* gt, const uint8_t* d_in, const uint64_t* d_
     const unsigned grid = grid_for(nchunks);
     const size_t lds = gt->lds_bytes;
     if (gt->lds_bytes && t.fast)
-        k_decode<Sym, true, true><<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, true, true)<<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
     else if (gt->lds_bytes)
-        k_decode<Sym, true, false><<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, true, false)<<<grid, kBlock, lds, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
     else if (t.fast)
-        k_decode<Sym, false, true><<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, false, true)<<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
     else
-        k_decode<Sym, false, false><<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
+        LAUNCH_DECODE_GENERIC(log, false, false)<<<grid, kBlock, 0, s>>>(t, d_in, d_offsets, slot_cap, d_lens, 0, 0, d_starts, 0, nchunks, gen_kind, out, d_status, ini);
     HIP_TRY(hipGetLastError());
     return ANS_OK;
 }

@@ -1,0 +1,45 @@
+// ans_launchlog.hpp — the launch record of a GPU context (ans_ctx.hpp ans_gpu::last), written by
+// the launchers of the bulk coders and read by ans_gpu_last_launch (include/ans_capi.h).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+// The coder kernels a context's last launcher call started, in launch order, with the template
+// arguments its ladder chose (ans_gpu_last_launch formats them).  A launcher clears the record on
+// entry and each launch site adds its entry from the same arguments that instantiate the kernel
+// (the LAUNCH_* macros of ans_launch_impl.hpp, menc_of / mdec_of, the exact kernels' dev_*), so
+// the record names what ran.  Plain data, no heap, nothing formatted on the launch path.
+enum LaunchKind : uint8_t {
+    kRecEncode,         // fast::k_encode      a = {KMAX, kK32, kGlobalRows, kVar, kNR, kM24}
+    kRecEncodeW,        // fast::k_encode_w    a = {kK32, kPack, kSa, kVar, kNR}
+    kRecDecode,         // fast::k_decode      a = {SPP, kMode, kP24, kJ4, kVar, kNR}
+    kRecDecodeW,        // fast::k_decode_w    a = {kCompact, kPrefix, kVar, kP24, kNR}
+    kRecDecodeG,        // fast::k_decode_g    a = {kNR}
+    kRecEncodeGeneric,  // k_encode (one lane per chunk)  a = {kLds, kFast}
+    kRecDecodeGeneric,  // k_decode (one lane per chunk)  a = {kLds, kFast}
+    kRecMenc,           // mfast::k_menc<IndepModel>  a = {SPP, kL, kRes, R (renorm screen), NR}
+    kRecMdec,           // mfast::k_mdec<IndepModel>  a = {SPP, kL, kRes, kLean, NR}
+    kRecEncode64,       // the exact kernels over a table set (ans_codecs.hip)
+    kRecDecode64,
+    kRecPush64,
+    kRecPop64,
+};
+struct LaunchRec {
+    uint8_t kind;
+    uint8_t sym_bytes;
+    int16_t a[6];
+};
+struct LaunchLog {
+    static constexpr uint32_t kCap = 8;  // (a call starts at most three coder kernels)
+    uint32_t n = 0;                      // launches since the clear (entries past kCap are counted only)
+    LaunchRec r[kCap] = {};
+    void clear() { n = 0; }
+    void add(LaunchKind kind, size_t sym_bytes, int a0 = 0, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0, int a5 = 0) {
+        if (n < kCap)
+            r[n] = LaunchRec{kind, static_cast<uint8_t>(sym_bytes),
+                             {static_cast<int16_t>(a0), static_cast<int16_t>(a1), static_cast<int16_t>(a2),
+                              static_cast<int16_t>(a3), static_cast<int16_t>(a4), static_cast<int16_t>(a5)}};
+        ++n;
+    }
+};

@@ -7,6 +7,7 @@
 
 #include <type_traits>
 
+#include "ans_launchlog.hpp"
 #include "ans_mfast.hpp"
 
 namespace shuffle_coding {
@@ -38,6 +39,7 @@ struct EncArgs {
     uint32_t* st;
     ChunkInit ini;
     hipStream_t s;
+    LaunchLog* log = nullptr;  // the context's launch record (Independent calls), or NULL
 };
 struct DecArgs {
     const uint8_t* in;
@@ -52,16 +54,32 @@ struct DecArgs {
     uint32_t* st;
     ChunkInit ini;
     hipStream_t s;
+    LaunchLog* log = nullptr;
+};
+// The launch record's view of a model: IndepModel's template arguments (the codecs whose ladders
+// the record covers); the IID models' launches are not recorded.
+template <class M>
+struct ModelRec {
+    static constexpr bool kIndep = false;
+};
+template <bool kRare, int kNR, uint32_t kTabD, bool kLean, uint32_t kTabEnc>
+struct ModelRec<IndepModel<kRare, kNR, kTabD, kLean, kTabEnc>> {
+    static constexpr bool kIndep = true;
+    static constexpr int rare = kRare, nr = kNR, lean = kLean;
 };
 // the launch of one instantiation: the tag arguments give Sym as a value and SPP as an Spp<N>
 template <int N>
 using Spp = std::integral_constant<int, N>;
 template <class M, int kL = kLanes, bool kRes = false, typename Sym, class P>
 void menc_of(const M& md, const EncArgs& a, uint32_t lds, Sym, P) {
+    if constexpr (ModelRec<M>::kIndep)
+        if (a.log) a.log->add(kRecMenc, sizeof(Sym), P::value, kL, kRes, ModelRec<M>::rare, ModelRec<M>::nr);
     menc<M, Sym, P::value, kL, kRes>(md, a.syms, a.tids, a.L, a.nfull, a.slots, a.cap, a.lens, a.st, a.ini, lds, a.s);
 }
 template <class M, int kL = kLanes, bool kRes = false, typename Sym, class P>
 void mdec_of(const M& md, const DecArgs& a, uint32_t lds, Sym, P) {
+    if constexpr (ModelRec<M>::kIndep)
+        if (a.log) a.log->add(kRecMdec, sizeof(Sym), P::value, kL, kRes, ModelRec<M>::lean, ModelRec<M>::nr);
     mdec<M, Sym, P::value, kL, kRes>(md, a.in, a.cap, a.offs, a.lens, a.tids, a.L, a.nfull, a.gen_kind, a.out, a.st, a.ini,
                                      lds, a.s);
 }

@@ -123,7 +123,10 @@ def test_u_domain_decoder_bit_exact(gpu, which):
         target = 400_000_000 if which == "shift_18" else 800_000_000
         masses = rng.integers(1 << 20, 1 << 23, 256).astype(np.uint64)
         masses = (masses * target // int(masses.sum())).astype(np.uint64)
-    else:  # masses of a few units beside large ones: kmax 4, half-unit points
+    else:  # masses of a few units beside large ones.  norm is about 2^23, so K is about 2^33 and
+        # even a mass of 1 has p K 2^32 >= 2^64: kmax 3 (whole-unit points), and the sixteen tiny
+        # masses crowd one bucket, so the table decodes through kModeFar, not the u-domain image.
+        # The kmax-4 half-unit u-domain decoder runs in test_gpu_variant_census.py (std_k4_u)
         masses = np.concatenate([rng.integers(1, 4, 16), rng.integers(1 << 12, 1 << 16, 240)]).astype(np.uint64)
     assert int(masses.sum()) < (1 << 31)
     gt = A.GpuTable(gpu, A.Categorical(masses))
