@@ -4,7 +4,8 @@
 // host because the reference drives them one symbol at a time from sequential callers
 // (src/recursive/mod.rs:117-148, src/recursive/prefix_orbit.rs:95-110): there is no
 // data parallelism inside one message.  The data-parallel path is section 4
-// (ans_kernels.hip); nothing here is a fallback for it.
+// (ans_pipe.hip for host buffers, ans_kernels.hip for device ones); nothing here is a fallback
+// for it.
 #include <new>
 
 #include "ans_table.hpp"

@@ -1,5 +1,6 @@
 // ans_ctx.hpp — the GPU context and table handles behind the C ABI (include/ans_capi.h),
-// shared by the HIP translation units of the library (ans_kernels.hip, ans_graph.hip).
+// shared by the HIP translation units of the library (ans_kernels.hip, ans_pipe.hip,
+// ans_graph.hip, ans_codecs*.hip and the launch units).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,45 +16,15 @@
 
 using namespace shuffle_coding;
 
-// Host-buffer pipeline (ans_gpu_encode_chunks / ans_gpu_decode_chunks): batches of chunks
-// flow through kPipeDepth workspace slots, so that the H2D copy of batch b+1, the kernels of
-// batch b and the D2H copy of batch b-1 overlap.  Kernels alternate between
-// two compute streams (the context's and s_comp2): a batch's kernels occupy few CUs for about
-// one chain latency (~1 ms for 4096-symbol chunks), so consecutive batches must overlap too.
-// The three pipeline streams each get a hardware queue of their own (CU-masked queues are
-// never shared; ans_kernels.hip own_queue_stream).  The workspace persists in the context and
-// grows on demand.
-constexpr int kPipeDepthMax = 8;  // workspace slots: ANS_PIPE_DEPTH (default kPipeDepth) at creation
-constexpr int kPipeDepth = 6;
-struct PipeSlot {
-    void* d_syms = nullptr;     // batch symbols
-    uint8_t* d_slots = nullptr; // batch streams in the slot layout
-    uint8_t* d_dense = nullptr; // batch streams, dense (encode output / decode input)
-    uint32_t* d_lens = nullptr;
-    uint64_t* d_offs = nullptr;  // batch offsets (+ total at [nchunks] after encode)
-    uint32_t* h_lens = nullptr;  // pinned staging
-    uint64_t* h_offs = nullptr;  // pinned staging
-    hipEvent_t ev_in = nullptr, ev_comp = nullptr, ev_meta = nullptr, ev_out = nullptr;
-    bool used = false;
-};
-struct HostPipe {
-    hipStream_t s_in = nullptr, s_out = nullptr, s_comp2 = nullptr;
-    PipeSlot slot[kPipeDepthMax];
-    int depth = kPipeDepth;  // slots in use
-    uint32_t* d_status = nullptr;
-    size_t cap_syms = 0, cap_slots = 0, cap_dense = 0, cap_chunks = 0;  // per slot
-    // page-locked callers (device-driven copies): per-call chunk metadata and the carry
-    uint64_t* h_meta = nullptr;  // mapped host staging: offsets[nchunks], lens[nchunks]
-    size_t cap_meta = 0;
-    uint64_t* d_acc = nullptr;   // running container offset across batches
-    hipEvent_t ev_scan = nullptr;
-};
+// The workspace of the host-buffer pipeline (ans_gpu_encode_chunks / ans_gpu_decode_chunks,
+// DESIGN.md §8): defined, built on the first host-buffer call and used in ans_pipe.hip alone.
+struct HostPipe;
 
 struct ans_gpu {
     int device;
     int ncu;  // compute units (launchers size per-CU LDS use by it)
     hipStream_t stream;
-    HostPipe* pipe;
+    HostPipe* pipe;        // null until the first host-buffer call; released by ans_pipe_free
     uint64_t batch_bytes;  // symbol bytes per pipeline batch (0 = default)
     void* d_scratch;       // device scratch of the device-resident graph calls (ans_graph.hip)
     size_t cap_scratch;
@@ -90,6 +61,9 @@ struct ans_gpu_table {
     catch (...) { return ANS_E_ARG; }
 #define ANS_CATCH_VOID \
     catch (...) {}
+
+// Releases g->pipe (ans_pipe.hip); ans_gpu_free's part of the pipeline.
+__attribute__((visibility("hidden"))) void ans_pipe_free(ans_gpu* g);
 
 // Variable-chunk encode of device-resident symbols into a host container (ans_kernels.hip):
 // the body of ans_gpu_encode_var_chunks; starts is a host array of nchunks + 1 entries.

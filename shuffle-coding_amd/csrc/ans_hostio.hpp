@@ -1,5 +1,6 @@
 // ans_hostio.hpp — host-side staging shared by the synchronous host-buffer entries of
-// ans_kernels.hip, ans_codecs.hip and ans_graph.hip (host code only; never in a timed path):
+// ans_kernels.hip, ans_pipe.hip, ans_codecs.hip and ans_graph.hip (host code only; the pipeline
+// takes its argument checks and status read from here, its copies are its own):
 // argument checks, the RAII device buffer, the decode head (chunk table checked and uploaded
 // with the container) and the encode tail (slots packed into the caller's container).
 #pragma once

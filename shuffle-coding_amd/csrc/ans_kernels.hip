@@ -1,15 +1,11 @@
-// ans_kernels.hip — MI355X (gfx950) rANS encode / decode of independent chunks.
-//
-// One lane owns one chunk = one reference Message (Message::zeros(), src/ans.rs:292)
-// coded with IID<Categorical> (src/codec.rs:415-424) through the blanket
-// Distribution push/pop (src/ans.rs:96-116) and flattened (src/ans.rs:255-260).
-// The bytes a lane writes are exactly that message's flattened tail.
-//
-// Layout in HBM:
-//   symbols  : the caller's array, chunk j = [j*L, min(n, (j+1)*L))
-//   slots    : chunk j's stream at slots + j*slot_cap (slot_cap = worst case, 16-B multiple)
-//   lens     : u32 per chunk
-//   table    : DevSym[nsym+1] (+ u16 icdf buckets), staged into LDS when it fits.
+// ans_kernels.hip — what surrounds the coder kernels of the Categorical tables (the coders
+// themselves are in the launch units, ans_launch.hpp; the host-buffer pipeline in ans_pipe.hip):
+//   * the copy and pack kernels between the slot layout and a dense container (k_compact,
+//     k_expand), the tiled length scan of the device-resident dense container
+//     (§3.4c), k_span_stats and the renorm self-check k_check_renorm;
+//   * build_fast_table: the fast kernels' tables derived from a Categorical (ans_table.hpp);
+//   * the C ABI's context and table entries (ans_gpu_create, ans_gpu_table_create, ...), its
+//     device-resident entries (ans_dev_*) and the variable-chunk host entries.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,7 +18,6 @@
 #include "ans_hostio.hpp"
 #include "ans_kcommon.hpp"
 #include "ans_launch.hpp"
-#include "ans_scan.hpp"
 
 using namespace shuffle_coding::launch;
 
@@ -620,566 +615,6 @@ int build_fast_table(ans_gpu_table* gt, const Categorical& cat) {
     return ANS_OK;
 }
 
-// ------------------------------------------------------------------ host-buffer pipeline
-
-constexpr int kPipeScattered = -1;
-
-// the workspace slots in use
-struct SlotRange {
-    PipeSlot* a;
-    PipeSlot* b;
-    PipeSlot* begin() const { return a; }
-    PipeSlot* end() const { return b; }
-};
-inline SlotRange slots_of(HostPipe* p) { return {p->slot, p->slot + p->depth}; }
-
-void pipe_release(HostPipe* p) {
-    for (PipeSlot& s : slots_of(p)) {
-        (void)hipFree(s.d_syms);
-        (void)hipFree(s.d_slots);
-        (void)hipFree(s.d_dense);
-        (void)hipFree(s.d_lens);
-        (void)hipFree(s.d_offs);
-        (void)hipHostFree(s.h_lens);
-        (void)hipHostFree(s.h_offs);
-        s.d_syms = s.d_slots = s.d_dense = nullptr;
-        s.d_syms = nullptr;
-        s.d_lens = nullptr;
-        s.d_offs = nullptr;
-        s.h_lens = nullptr;
-        s.h_offs = nullptr;
-        s.used = false;
-    }
-    p->cap_syms = p->cap_slots = p->cap_dense = p->cap_chunks = 0;
-}
-
-void pipe_free(ans_gpu* g) {
-    HostPipe* p = g->pipe;
-    if (!p) return;
-    (void)hipDeviceSynchronize();
-    pipe_release(p);
-    for (PipeSlot& s : slots_of(p)) {
-        (void)hipEventDestroy(s.ev_in);
-        (void)hipEventDestroy(s.ev_comp);
-        (void)hipEventDestroy(s.ev_meta);
-        (void)hipEventDestroy(s.ev_out);
-    }
-    (void)hipFree(p->d_status);
-    (void)hipFree(p->d_acc);
-    if (p->h_meta) (void)hipHostFree(p->h_meta);
-    if (p->ev_scan) (void)hipEventDestroy(p->ev_scan);
-    (void)hipStreamDestroy(p->s_in);
-    (void)hipStreamDestroy(p->s_out);
-    (void)hipStreamDestroy(p->s_comp2);
-    delete p;
-    g->pipe = nullptr;
-}
-
-// A stream on a hardware queue of its own, its kernels restricted to the CUs of `pattern`
-// (repeated over the mask words): a CU-masked queue is never shared.  The runtime moves
-// device-to-host bytes with blit kernels on the copy stream's queue; with GPU_MAX_HW_QUEUES = 4
-// and five streams in the process that queue was shared with the second compute stream, whose
-// decode kernels then waited for every blit (tools/host_timeline.py), and a blit spread over
-// all CUs leaves none free for a decode workgroup (which fills a CU's VGPRs and LDS).
-hipError_t own_queue_stream(hipStream_t* s, uint32_t pattern) {
-    int dev = 0, ncu = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess || ncu <= 0) return e != hipSuccess ? e : hipErrorInvalidDevice;
-    std::vector<uint32_t> mask((ncu + 31) / 32, pattern);
-    if (ncu % 32) mask.back() &= (1u << (ncu % 32)) - 1u;
-    return hipExtStreamCreateWithCUMask(s, static_cast<uint32_t>(mask.size()), mask.data());
-}
-
-// The context's pipeline with per-slot room for `syms` symbol bytes, `slots` slot bytes,
-// `dense` dense bytes and `chunks` chunks (reallocated, after draining, when it must grow).
-int pipe_get(ans_gpu* g, size_t syms, size_t slots, size_t dense, size_t chunks, HostPipe** out) {
-    if (!g->pipe) {
-        auto* p = new (std::nothrow) HostPipe{};
-        if (!p) return ANS_E_ALLOC;
-        g->pipe = p;
-        if (const char* e = getenv("ANS_PIPE_DEPTH")) p->depth = std::min(kPipeDepthMax, std::max(2, atoi(e)));
-        HIP_TRY(own_queue_stream(&p->s_in, ~0u));
-        HIP_TRY(own_queue_stream(&p->s_out, 0x11111111u));  // device-to-host blits on a quarter of the CUs
-        HIP_TRY(own_queue_stream(&p->s_comp2, ~0u));
-        for (PipeSlot& s : slots_of(p)) {
-            HIP_TRY(hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&s.ev_comp, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&s.ev_meta, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
-        }
-        HIP_TRY(hipMalloc(&p->d_status, sizeof(uint32_t)));
-    }
-    HostPipe* p = g->pipe;
-    if (syms > p->cap_syms || slots > p->cap_slots || dense > p->cap_dense || chunks > p->cap_chunks) {
-        HIP_TRY(hipDeviceSynchronize());
-        syms = std::max(syms, p->cap_syms);
-        slots = std::max(slots, p->cap_slots);
-        dense = std::max(dense, p->cap_dense);
-        chunks = std::max(chunks, p->cap_chunks);
-        pipe_release(p);
-        for (PipeSlot& s : slots_of(p)) {
-            HIP_TRY(hipMalloc(&s.d_syms, syms + 16));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_slots), slots + 16));
-            // + 256: k_decode_g (the non-wide large-alphabet decoder, norm < 2^22) reads whole
-            // aligned 128-B lines around each stream, so the last stream of a batch may touch the
-            // line past its span (k_decode and k_decode_w read only the stream's own bytes)
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_dense), dense + 256));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_lens), sizeof(uint32_t) * chunks + 16));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_offs), sizeof(uint64_t) * (chunks + 1) + 16));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_lens), sizeof(uint32_t) * chunks + 16));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_offs), sizeof(uint64_t) * (chunks + 1) + 16));
-        }
-        p->cap_syms = syms;
-        p->cap_slots = slots;
-        p->cap_dense = dense;
-        p->cap_chunks = chunks;
-    }
-    for (PipeSlot& s : slots_of(p)) s.used = false;
-    *out = p;
-    return ANS_OK;
-}
-
-// Chunks per batch: about batch_bytes (default 128 MiB) of symbols.  A batch's kernels take
-// about one chain latency (~1 ms) whatever its size until it fills the GPU, so batches must
-// be large; 128 MiB batches through six workspace slots measured best for the round trip
-// (tools/gpu_pipe_sweep.sh), with the workspace of three 256-MiB slots.
-constexpr uint64_t kPipeBatchBytes = 128ull << 20;
-uint64_t pipe_batch_chunks(const ans_gpu* g, uint64_t nchunks, uint64_t chunk_bytes) {
-    const uint64_t target = g->batch_bytes ? g->batch_bytes : kPipeBatchBytes;
-    uint64_t b = target / (chunk_bytes ? chunk_bytes : 1);
-    if (b < 1) b = 1;
-    return b < nchunks ? b : nchunks;
-}
-
-// Batch boundaries (chunk indices, first 0, last nchunks): batches of B chunks.  (Batches
-// ramping up and down in size at the ends were measured too: with enough workspace slots
-// they gained nothing over equal 128-MiB batches)
-std::vector<uint64_t> pipe_cuts(uint64_t nchunks, uint64_t B) {
-    std::vector<uint64_t> cuts{0};
-    for (uint64_t c = B; c < nchunks; c += B) cuts.push_back(c);
-    cuts.push_back(nchunks);
-    return cuts;
-}
-
-// Encode from host symbols into a host dense container.  Batch b: H2D (s_in) -> encode,
-// length scan, compaction, lengths D2H (compute stream b & 1); the host waits for batch
-// b-1's lengths only after batch b is queued, then queues b-1's dense D2H (s_out) at its
-// running offset.  With out == NULL (size query) nothing but the lengths comes back.
-template <typename Sym>
-int pipe_encode(ans_gpu_table* gt, const void* syms, uint64_t n, uint64_t chunk_len, uint8_t* out, uint64_t out_cap,
-                uint64_t* offsets, uint64_t* lens, uint64_t* total, fast::ChunkInit ini) {
-    constexpr uint64_t w = sizeof(Sym);
-    const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
-    uint64_t slot_cap = 0;
-    ans_gpu_slot_capacity(gt, chunk_len, &slot_cap);
-    const uint64_t B = pipe_batch_chunks(gt->g, nchunks, chunk_len * w);
-    HostPipe* p = nullptr;
-    int rc = pipe_get(gt->g, B * chunk_len * w, B * slot_cap, out ? B * slot_cap : 0, B, &p);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(p->d_status, 0, sizeof(uint32_t), gt->g->stream));
-    HIP_TRY(hipStreamSynchronize(gt->g->stream));
-    const std::vector<uint64_t> cuts = pipe_cuts(nchunks, B);
-    const uint64_t nbatch = cuts.size() - 1;
-    const auto* src = static_cast<const uint8_t*>(syms);
-    bool copy = out != nullptr;
-    int len_err = ANS_OK;
-    uint64_t acc = 0;
-    auto enqueue = [&](uint64_t b) -> int {
-        PipeSlot& s = p->slot[b % p->depth];
-        const hipStream_t sc = (b & 1) ? p->s_comp2 : gt->g->stream;
-        const uint64_t c0 = cuts[b], nc = cuts[b + 1] - c0, n0 = c0 * chunk_len;
-        const uint64_t nb = std::min(n - n0, nc * chunk_len);
-        if (s.used) HIP_TRY(hipStreamWaitEvent(p->s_in, s.ev_comp, 0));  // symbols of batch b - depth consumed
-        HIP_TRY(hipMemcpyAsync(s.d_syms, src + n0 * w, nb * w, hipMemcpyHostToDevice, p->s_in));
-        HIP_TRY(hipEventRecord(s.ev_in, p->s_in));
-        HIP_TRY(hipStreamWaitEvent(sc, s.ev_in, 0));
-        if (s.used) HIP_TRY(hipStreamWaitEvent(sc, s.ev_out, 0));  // dense bytes of batch b - depth copied out
-        int r = launch_encode<Sym>(gt, s.d_syms, nb, chunk_len, s.d_slots, slot_cap, s.d_lens, p->d_status, sc,
-                                   fast::ChunkInit{ini.kind, ini.seed + c0});
-        if (r) return r;
-        // the batch's stream offsets: offs[j] = sum of lens[0..j), offs[nc] = total (ans_scan.hpp)
-        k_excl_scan<<<1, 1024, 0, sc>>>(s.d_lens, nc, s.d_offs, s.d_offs + nc);
-        HIP_TRY(hipGetLastError());
-        if (copy) {
-            k_compact<<<grid_for(nc * 64), kBlock, 0, sc>>>(s.d_slots, slot_cap, s.d_lens, s.d_offs, nc, s.d_dense);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(s.ev_comp, sc));
-        HIP_TRY(hipMemcpyAsync(s.h_lens, s.d_lens, sizeof(uint32_t) * nc, hipMemcpyDeviceToHost, sc));
-        HIP_TRY(hipMemcpyAsync(s.h_offs, s.d_offs + nc, sizeof(uint64_t), hipMemcpyDeviceToHost, sc));
-        HIP_TRY(hipEventRecord(s.ev_meta, sc));
-        s.used = true;
-        return ANS_OK;
-    };
-    auto finish = [&](uint64_t b) -> int {
-        PipeSlot& s = p->slot[b % p->depth];
-        const uint64_t c0 = cuts[b], nc = cuts[b + 1] - c0;
-        HIP_TRY(hipEventSynchronize(s.ev_meta));
-        const uint64_t bt = s.h_offs[0];
-        if (copy && acc + bt > out_cap) {
-            copy = false;  // keep coding to report the exact total
-            len_err = ANS_E_LEN;
-        }
-        if (copy && bt) HIP_TRY(hipMemcpyAsync(out + acc, s.d_dense, bt, hipMemcpyDeviceToHost, p->s_out));
-        HIP_TRY(hipEventRecord(s.ev_out, p->s_out));
-        uint64_t o = acc;
-        for (uint64_t j = 0; j < nc; ++j) {
-            if (out) {
-                offsets[c0 + j] = o;
-                lens[c0 + j] = s.h_lens[j];
-            }
-            o += s.h_lens[j];
-        }
-        acc = o;
-        return ANS_OK;
-    };
-    for (uint64_t b = 0; b < nbatch; ++b) {
-        if ((rc = enqueue(b))) return rc;
-        if (b > 0 && (rc = finish(b - 1))) return rc;
-    }
-    if (nbatch && (rc = finish(nbatch - 1))) return rc;
-    HIP_TRY(hipStreamSynchronize(p->s_out));
-    HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    if ((rc = read_status(gt->g, p->d_status, gt->g->stream))) return rc;
-    *total = acc;
-    return len_err;
-}
-
-// Decode a host dense container into host symbols.  Batch b: its byte span and rebased
-// offsets/lengths H2D (s_in) -> decode of the span in place (compute stream b & 1; the
-// decoders read a dense container at any alignment, fast::DecChain::start) -> symbols D2H
-// (s_out).  No host synchronisation inside the loop beyond staging reuse.
-// Returns kPipeScattered when some batch's streams spread over more than twice its slot bytes
-// (a container that is not dense); the caller then takes the whole-buffer path.
-template <typename Sym>
-int pipe_decode(ans_gpu_table* gt, const uint8_t* in, const uint64_t* offsets, const uint32_t* l32, uint64_t slot_cap,
-                uint64_t n, uint64_t chunk_len, int gen_kind, void* out, fast::ChunkInit ini) {
-    constexpr uint64_t w = sizeof(Sym);
-    const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
-    const uint64_t B = pipe_batch_chunks(gt->g, nchunks, chunk_len * w);
-    const std::vector<uint64_t> cuts = pipe_cuts(nchunks, B);
-    const uint64_t nbatch = cuts.size() - 1;
-    std::vector<uint64_t> lo(nbatch), span(nbatch);
-    uint64_t max_span = 0;
-    for (uint64_t b = 0; b < nbatch; ++b) {
-        const uint64_t c0 = cuts[b], c1 = cuts[b + 1];
-        uint64_t l = ~0ull, h = 0;
-        for (uint64_t j = c0; j < c1; ++j) {
-            l = std::min(l, offsets[j]);
-            h = std::max(h, offsets[j] + l32[j]);
-        }
-        lo[b] = l;
-        span[b] = h - l;
-        max_span = std::max(max_span, span[b]);
-    }
-    if (max_span > 2 * B * slot_cap) return kPipeScattered;
-    HostPipe* p = nullptr;
-    int rc = pipe_get(gt->g, B * chunk_len * w, B * slot_cap, max_span, B, &p);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(p->d_status, 0, sizeof(uint32_t), gt->g->stream));
-    HIP_TRY(hipStreamSynchronize(gt->g->stream));
-    auto* dst = static_cast<uint8_t*>(out);
-    for (uint64_t b = 0; b < nbatch; ++b) {
-        PipeSlot& s = p->slot[b % p->depth];
-        const hipStream_t sc = (b & 1) ? p->s_comp2 : gt->g->stream;
-        const uint64_t c0 = cuts[b], nc = cuts[b + 1] - c0, n0 = c0 * chunk_len;
-        const uint64_t nb = std::min(n - n0, nc * chunk_len);
-        if (s.used) {
-            HIP_TRY(hipEventSynchronize(s.ev_in));  // staging of batch b - depth uploaded
-            HIP_TRY(hipStreamWaitEvent(p->s_in, s.ev_out, 0));  // its buffers drained
-        }
-        std::memcpy(s.h_lens, l32 + c0, sizeof(uint32_t) * nc);
-        for (uint64_t j = 0; j < nc; ++j) s.h_offs[j] = offsets[c0 + j] - lo[b];  // into the batch's span
-        if (span[b]) HIP_TRY(hipMemcpyAsync(s.d_dense, in + lo[b], span[b], hipMemcpyHostToDevice, p->s_in));
-        HIP_TRY(hipMemcpyAsync(s.d_lens, s.h_lens, sizeof(uint32_t) * nc, hipMemcpyHostToDevice, p->s_in));
-        HIP_TRY(hipMemcpyAsync(s.d_offs, s.h_offs, sizeof(uint64_t) * nc, hipMemcpyHostToDevice, p->s_in));
-        HIP_TRY(hipEventRecord(s.ev_in, p->s_in));
-        HIP_TRY(hipStreamWaitEvent(sc, s.ev_in, 0));
-        if ((rc = launch_decode<Sym>(gt, s.d_dense, s.d_offs, slot_cap, s.d_lens, nb, chunk_len, gen_kind, s.d_syms,
-                                     p->d_status, sc, fast::ChunkInit{ini.kind, ini.seed + c0})))
-            return rc;
-        HIP_TRY(hipEventRecord(s.ev_comp, sc));
-        HIP_TRY(hipStreamWaitEvent(p->s_out, s.ev_comp, 0));
-        HIP_TRY(hipMemcpyAsync(dst + n0 * w, s.d_syms, nb * w, hipMemcpyDeviceToHost, p->s_out));
-        HIP_TRY(hipEventRecord(s.ev_out, p->s_out));
-        s.used = true;
-    }
-    HIP_TRY(hipStreamSynchronize(p->s_out));
-    HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    return read_status(gt->g, p->d_status, gt->g->stream);
-}
-
-// ---- page-locked host buffers: the GPU moves the bytes itself (no runtime copy calls)
-//
-// Page-locked host memory is mapped into the GPU's address space, so copy kernels can read
-// and write it across PCIe directly (tools/pinned_probe.hip: ~41 GB/s each way with both
-// directions in flight, ~55 GB/s alone).  The per-batch work then needs no host
-// synchronisation at all: batch offsets are scanned and carried on the device, and the
-// copy-out kernel reads its destination offset and size from device memory.
-
-// Copy engine for page-locked buffers: the runtime's copies (default: measured faster,
-// DESIGN.md §8) or these kernels (ANS_PIPE_COPY=kernel, the A/B switch behind that table).
-bool pipe_kernel_copies() {
-    const char* e = getenv("ANS_PIPE_COPY");  // read per call (tests switch it)
-    return e && std::strcmp(e, "kernel") == 0;
-}
-
-// Device-visible address of a page-locked host pointer (nullptr for pageable memory).
-uint8_t* mapped_ptr(const void* p) {
-    if (!p) return nullptr;
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    if (a.type != hipMemoryTypeHost || !a.devicePointer) return nullptr;
-    return static_cast<uint8_t*>(a.devicePointer);
-}
-
-constexpr unsigned kXferGrid = 128;  // workgroups per copy kernel (probe: 64-256 saturate PCIe)
-
-// dst[0..bytes) = src[0..bytes) between device memory and mapped host memory; 16-byte
-// accesses when dst and src agree mod 16 (the pipeline arranges that), bytes otherwise.
-__device__ __forceinline__ void xfer_bytes(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t bytes) {
-    const uint64_t tid = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const uint64_t nth = static_cast<uint64_t>(gridDim.x) * blockDim.x;
-    if (((reinterpret_cast<uintptr_t>(dst) ^ reinterpret_cast<uintptr_t>(src)) & 15) == 0) {
-        const uint64_t head = std::min<uint64_t>(bytes, (16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15);
-        if (tid < head) dst[tid] = src[tid];
-        const uint64_t n16 = (bytes - head) / 16;
-        uint4* d = reinterpret_cast<uint4*>(dst + head);
-        const uint4* s = reinterpret_cast<const uint4*>(src + head);
-        for (uint64_t i = tid; i < n16; i += nth) d[i] = s[i];
-        const uint64_t done = head + 16 * n16;
-        if (tid < bytes - done) dst[done + tid] = src[done + tid];
-    } else {
-        for (uint64_t i = tid; i < bytes; i += nth) dst[i] = src[i];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_xfer(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t bytes) {
-    xfer_bytes(dst, src, bytes);
-}
-
-// Batch scan for the mapped encoder: the batch's offsets (ans_scan.hpp) plus the running
-// container offset.  base = *acc (the bytes of all earlier batches), *acc += total; offs[n] =
-// total, offs[n+1] = base; each chunk's absolute offset and length go to the host arrays.
-__global__ __launch_bounds__(1024) void k_scan_carry(const uint32_t* __restrict__ lens, uint64_t n,
-                                                     uint64_t* __restrict__ offs, uint64_t* __restrict__ acc,
-                                                     uint64_t* __restrict__ h_offs, uint64_t* __restrict__ h_lens) {
-    __shared__ uint64_t base;
-    const uint32_t t = threadIdx.x;
-    if (t == 0) base = *acc;
-    const uint64_t total = block_excl_scan(lens, n, offs);  // (its barriers publish base)
-    if (t == 1023) {
-        offs[n] = total;
-        offs[n + 1] = base;
-        *acc = base + total;
-    }
-    __syncthreads();
-    for (uint64_t i = t; i < n; i += 1024) {  // coalesced writes across PCIe
-        h_offs[i] = base + offs[i];
-        h_lens[i] = lens[i];
-    }
-}
-
-// Slots -> dense bytes at dense + sh + offs[c], sh = (out + base) & 15 so that the copy-out
-// kernel's source and destination agree mod 16.
-__global__ __launch_bounds__(kBlock) void k_compact_at(const uint8_t* __restrict__ slots, uint64_t slot_cap,
-                                                       const uint32_t* __restrict__ lens,
-                                                       const uint64_t* __restrict__ offs, uint64_t nchunks,
-                                                       uintptr_t out_addr, uint8_t* __restrict__ dense) {
-    const uint64_t c = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / 64;
-    const uint32_t lane = threadIdx.x & 63;
-    if (c >= nchunks) return;
-    const uint64_t sh = (out_addr + offs[nchunks + 1]) & 15;
-    const uint8_t* s = slots + c * slot_cap;
-    uint8_t* d = dense + sh + offs[c];
-    wave_copy(d, s, static_cast<uint32_t>(min<uint64_t>(lens[c], slot_cap)), lane);
-}
-
-// Copy-out of one encoded batch to out + base (size and base from the scan); a batch that
-// would overrun out_cap is not copied and flags ANS_E_LEN (coding continues, so the exact
-// total is still known).
-__global__ __launch_bounds__(256) void k_xfer_out(uint8_t* __restrict__ out, uint64_t out_cap,
-                                                  const uint8_t* __restrict__ dense, const uint64_t* __restrict__ offs,
-                                                  uint64_t nchunks, uint32_t* __restrict__ status) {
-    const uint64_t total = offs[nchunks], base = offs[nchunks + 1];
-    if (base + total > out_cap) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, 1u << ANS_E_LEN);
-        return;
-    }
-    const uint64_t sh = (reinterpret_cast<uintptr_t>(out) + base) & 15;
-    xfer_bytes(out + base, dense + sh, total);
-}
-
-// Dense batch bytes (at dense + sh, sh = (in + lo) & 15) -> slots; the chunk offsets and
-// lengths are read from the mapped host staging, lengths also land in d_lens for the decoder.
-__global__ __launch_bounds__(kBlock) void k_expand_mapped(const uint8_t* __restrict__ dense, uint64_t sh, uint64_t lo,
-                                                          const uint64_t* __restrict__ h_offs,
-                                                          const uint64_t* __restrict__ h_lens, uint64_t nchunks,
-                                                          uint32_t* __restrict__ d_lens, uint8_t* __restrict__ slots,
-                                                          uint64_t slot_cap) {
-    const uint64_t c = (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / 64;
-    const uint32_t lane = threadIdx.x & 63;
-    if (c >= nchunks) return;
-    const uint64_t off = h_offs[c];
-    const uint32_t len = static_cast<uint32_t>(h_lens[c]);
-    if (lane == 0) d_lens[c] = len;
-    const uint8_t* s = dense + sh + (off - lo);
-    uint8_t* d = slots + c * slot_cap;
-    wave_copy(d, s, len, lane);
-}
-
-// Host staging (mapped) for 2 x u64 per chunk of a whole call, and the device carry word.
-int pipe_meta(HostPipe* p, uint64_t nchunks) {
-    if (!p->d_acc) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d_acc), 16));
-    if (!p->ev_scan) HIP_TRY(hipEventCreateWithFlags(&p->ev_scan, hipEventDisableTiming));
-    if (nchunks > p->cap_meta) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (p->h_meta) (void)hipHostFree(p->h_meta);
-        p->h_meta = nullptr;
-        p->cap_meta = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->h_meta), 2 * sizeof(uint64_t) * nchunks + 16));
-        p->cap_meta = nchunks;
-    }
-    return ANS_OK;
-}
-
-// Encode with page-locked symbols and container.  Batch b: symbols in (k_xfer on s_in) ->
-// encode, carried scan, compaction (compute stream b & 1) -> container bytes out
-// (k_xfer_out on s_out).  The host only waits at the end.
-template <typename Sym>
-int pipe_encode_mapped(ans_gpu_table* gt, const uint8_t* syms_dev, uint64_t n, uint64_t chunk_len, uint8_t* out_dev,
-                       uint64_t out_cap, uint64_t* offsets, uint64_t* lens, uint64_t* total, fast::ChunkInit ini) {
-    constexpr uint64_t w = sizeof(Sym);
-    const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
-    uint64_t slot_cap = 0;
-    ans_gpu_slot_capacity(gt, chunk_len, &slot_cap);
-    const uint64_t B = pipe_batch_chunks(gt->g, nchunks, chunk_len * w);
-    HostPipe* p = nullptr;
-    int rc = pipe_get(gt->g, B * chunk_len * w, B * slot_cap, out_dev ? B * slot_cap + 16 : 0, B + 1, &p);
-    if (rc || (rc = pipe_meta(p, nchunks))) return rc;
-    uint64_t* h_offs = p->h_meta;
-    uint64_t* h_lens = p->h_meta + nchunks;
-    const hipStream_t s0 = gt->g->stream;
-    HIP_TRY(hipMemsetAsync(p->d_status, 0, sizeof(uint32_t), s0));
-    HIP_TRY(hipMemsetAsync(p->d_acc, 0, sizeof(uint64_t), s0));
-    HIP_TRY(hipStreamSynchronize(s0));
-    const uint64_t nbatch = (nchunks + B - 1) / B;
-    for (uint64_t b = 0; b < nbatch; ++b) {
-        PipeSlot& s = p->slot[b % p->depth];
-        const hipStream_t sc = (b & 1) ? p->s_comp2 : s0;
-        const uint64_t c0 = b * B, nc = std::min(B, nchunks - c0), n0 = c0 * chunk_len;
-        const uint64_t nb = std::min(n - n0, nc * chunk_len);
-        if (s.used) HIP_TRY(hipStreamWaitEvent(p->s_in, s.ev_comp, 0));  // symbols of batch b - depth consumed
-        k_xfer<<<kXferGrid, 256, 0, p->s_in>>>(static_cast<uint8_t*>(s.d_syms), syms_dev + n0 * w, nb * w);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(s.ev_in, p->s_in));
-        HIP_TRY(hipStreamWaitEvent(sc, s.ev_in, 0));
-        if (s.used) HIP_TRY(hipStreamWaitEvent(sc, s.ev_out, 0));  // dense bytes of batch b - depth copied out
-        if ((rc = launch_encode<Sym>(gt, s.d_syms, nb, chunk_len, s.d_slots, slot_cap, s.d_lens, p->d_status, sc,
-                                     fast::ChunkInit{ini.kind, ini.seed + c0})))
-            return rc;
-        if (b > 0) HIP_TRY(hipStreamWaitEvent(sc, p->ev_scan, 0));  // the carry runs in batch order
-        k_scan_carry<<<1, 1024, 0, sc>>>(s.d_lens, nc, s.d_offs, p->d_acc, h_offs + c0, h_lens + c0);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(p->ev_scan, sc));
-        if (out_dev) {
-            k_compact_at<<<grid_for(nc * 64), kBlock, 0, sc>>>(s.d_slots, slot_cap, s.d_lens, s.d_offs, nc,
-                                                               reinterpret_cast<uintptr_t>(out_dev), s.d_dense);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(s.ev_comp, sc));
-        HIP_TRY(hipStreamWaitEvent(p->s_out, s.ev_comp, 0));
-        if (out_dev) {
-            k_xfer_out<<<kXferGrid, 256, 0, p->s_out>>>(out_dev, out_cap, s.d_dense, s.d_offs, nc, p->d_status);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(s.ev_out, p->s_out));
-        s.used = true;
-    }
-    HIP_TRY(hipStreamSynchronize(p->s_out));
-    HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    HIP_TRY(hipStreamSynchronize(s0));
-    uint32_t bits = 0;
-    uint64_t acc = 0;
-    HIP_TRY(hipMemcpy(&bits, p->d_status, sizeof(bits), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&acc, p->d_acc, sizeof(acc), hipMemcpyDeviceToHost));
-    const int st = lowest_status(bits & ~(1u << ANS_E_LEN));
-    if (st) return st;
-    *total = acc;
-    if (!out_dev) return ANS_OK;
-    std::memcpy(offsets, h_offs, sizeof(uint64_t) * nchunks);
-    std::memcpy(lens, h_lens, sizeof(uint64_t) * nchunks);
-    return (bits & (1u << ANS_E_LEN)) ? ANS_E_LEN : ANS_OK;
-}
-
-// Decode from a page-locked container into page-locked symbols.  Batch b: its byte span in
-// (k_xfer on s_in) -> expansion (offsets and lengths read from the mapped staging) and
-// decode (compute stream b & 1) -> symbols out (k_xfer on s_out).  No host waits in the loop.
-template <typename Sym>
-int pipe_decode_mapped(ans_gpu_table* gt, const uint8_t* in_dev, const uint64_t* offsets, const uint32_t* l32,
-                       uint64_t slot_cap, uint64_t n, uint64_t chunk_len, int gen_kind, uint8_t* out_dev,
-                       fast::ChunkInit ini) {
-    constexpr uint64_t w = sizeof(Sym);
-    const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
-    const uint64_t B = pipe_batch_chunks(gt->g, nchunks, chunk_len * w);
-    const uint64_t nbatch = (nchunks + B - 1) / B;
-    std::vector<uint64_t> lo(nbatch), span(nbatch);
-    uint64_t max_span = 0;
-    for (uint64_t b = 0; b < nbatch; ++b) {
-        const uint64_t c0 = b * B, c1 = std::min(nchunks, c0 + B);
-        uint64_t l = ~0ull, h = 0;
-        for (uint64_t j = c0; j < c1; ++j) {
-            l = std::min(l, offsets[j]);
-            h = std::max(h, offsets[j] + l32[j]);
-        }
-        lo[b] = l;
-        span[b] = h - l;
-        max_span = std::max(max_span, span[b]);
-    }
-    if (max_span > 2 * B * slot_cap) return kPipeScattered;
-    HostPipe* p = nullptr;
-    int rc = pipe_get(gt->g, B * chunk_len * w, B * slot_cap, max_span + 16, B + 1, &p);
-    if (rc || (rc = pipe_meta(p, nchunks))) return rc;
-    uint64_t* h_offs = p->h_meta;
-    uint64_t* h_lens = p->h_meta + nchunks;
-    std::memcpy(h_offs, offsets, sizeof(uint64_t) * nchunks);
-    for (uint64_t j = 0; j < nchunks; ++j) h_lens[j] = l32[j];
-    const hipStream_t s0 = gt->g->stream;
-    HIP_TRY(hipMemsetAsync(p->d_status, 0, sizeof(uint32_t), s0));
-    HIP_TRY(hipStreamSynchronize(s0));
-    for (uint64_t b = 0; b < nbatch; ++b) {
-        PipeSlot& s = p->slot[b % p->depth];
-        const hipStream_t sc = (b & 1) ? p->s_comp2 : s0;
-        const uint64_t c0 = b * B, nc = std::min(B, nchunks - c0), n0 = c0 * chunk_len;
-        const uint64_t nb = std::min(n - n0, nc * chunk_len);
-        const uint64_t sh = reinterpret_cast<uintptr_t>(in_dev + lo[b]) & 15;
-        if (s.used) HIP_TRY(hipStreamWaitEvent(p->s_in, s.ev_out, 0));  // batch b - depth drained
-        k_xfer<<<kXferGrid, 256, 0, p->s_in>>>(s.d_dense + sh, in_dev + lo[b], span[b]);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(s.ev_in, p->s_in));
-        HIP_TRY(hipStreamWaitEvent(sc, s.ev_in, 0));
-        k_expand_mapped<<<grid_for(nc * 64), kBlock, 0, sc>>>(s.d_dense, sh, lo[b], h_offs + c0, h_lens + c0, nc,
-                                                              s.d_lens, s.d_slots, slot_cap);
-        HIP_TRY(hipGetLastError());
-        if ((rc = launch_decode<Sym>(gt, s.d_slots, nullptr, slot_cap, s.d_lens, nb, chunk_len, gen_kind, s.d_syms,
-                                     p->d_status, sc, fast::ChunkInit{ini.kind, ini.seed + c0})))
-            return rc;
-        HIP_TRY(hipEventRecord(s.ev_comp, sc));
-        HIP_TRY(hipStreamWaitEvent(p->s_out, s.ev_comp, 0));
-        k_xfer<<<kXferGrid, 256, 0, p->s_out>>>(out_dev + n0 * w, static_cast<const uint8_t*>(s.d_syms), nb * w);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(s.ev_out, p->s_out));
-        s.used = true;
-    }
-    HIP_TRY(hipStreamSynchronize(p->s_out));
-    HIP_TRY(hipStreamSynchronize(p->s_comp2));
-    return read_status(gt->g, p->d_status, s0);
-}
-
 }  // namespace
 
 // Variable-chunk encode of symbols already on the device (ans_ctx.hpp): the body of
@@ -1240,32 +675,6 @@ int ans_gpu_create(int device, ans_gpu** out) try {
     return ANS_OK;
 } ANS_CATCH
 
-int ans_host_alloc(size_t bytes, void** out) try {
-    if (!out) return ANS_E_ARG;
-    *out = nullptr;
-    if (hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
-        *out = nullptr;
-        return ANS_E_ALLOC;
-    }
-    return ANS_OK;
-} ANS_CATCH
-
-void ans_host_free(void* p) try {
-    if (p) (void)hipHostFree(p);
-} ANS_CATCH_VOID
-
-int ans_gpu_set_batch_bytes(ans_gpu* g, uint64_t batch_bytes) try {
-    if (!g) return ANS_E_ARG;
-    g->batch_bytes = batch_bytes;
-    return ANS_OK;
-} ANS_CATCH
-
-int ans_gpu_pipe_depth(const ans_gpu* g, int* depth) try {
-    if (!g || !depth) return ANS_E_ARG;
-    *depth = g->pipe ? g->pipe->depth : 0;
-    return ANS_OK;
-} ANS_CATCH
-
 // The launch record as text (include/ans_capi.h).  Formatting happens here, never on a launch path.
 int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) try {
     if (!g || !len) return ANS_E_ARG;
@@ -1316,7 +725,7 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
 void ans_gpu_free(ans_gpu* g) try {
     if (!g) return;
     (void)hipSetDevice(g->device);
-    pipe_free(g);
+    ans_pipe_free(g);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
     (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1796,103 +1205,6 @@ int ans_dev_status(ans_gpu* g, const uint32_t* d_status, void* stream, int* stat
     HIP_TRY(hipStreamSynchronize(s));
     *status = lowest_status(bits);
     return ANS_OK;
-} ANS_CATCH
-
-int ans_gpu_encode_chunks_ex(ans_gpu_table* gt, const void* syms, int sym_bytes, uint64_t n, uint64_t chunk_len,
-                             int gen_kind, uint64_t seed, uint8_t* out, uint64_t out_cap, uint64_t* offsets,
-                             uint64_t* lens, uint64_t* total) try {
-    (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width_u32(sym_bytes) || chunk_len == 0 || !total || !valid_kind(gen_kind)) return ANS_E_ARG;
-    const fast::ChunkInit ini{gen_kind, seed};
-    if (n && !syms) return ANS_E_ARG;
-    if (gt->ts64) {
-        const uint64_t nc = (n + chunk_len - 1) / chunk_len;
-        if (out && nc && (!offsets || !lens)) return ANS_E_ARG;
-        return ans_tableset_host_encode(gt->ts64, syms, sym_bytes, n, chunk_len, nullptr, nc, gen_kind, seed, out,
-                                        out_cap, offsets, lens, total);
-    }
-    const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
-    if (out && nchunks && (!offsets || !lens)) return ANS_E_ARG;
-    *total = 0;
-    if (nchunks == 0) return ANS_OK;
-    HIP_TRY(hipSetDevice(gt->g->device));
-    // page-locked symbols and container (or a size query): device-driven copies
-    uint8_t* syms_dev = pipe_kernel_copies() ? mapped_ptr(syms) : nullptr;
-    uint8_t* out_dev = out && syms_dev ? mapped_ptr(out) : nullptr;
-    if (syms_dev && (!out || out_dev)) {
-        return with_sym_type(sym_bytes, [&](auto t) {
-            return pipe_encode_mapped<decltype(t)>(gt, syms_dev, n, chunk_len, out_dev, out_cap, offsets, lens, total,
-                                                   ini);
-        });
-    }
-    return with_sym_type(sym_bytes, [&](auto t) {
-        return pipe_encode<decltype(t)>(gt, syms, n, chunk_len, out, out_cap, offsets, lens, total, ini);
-    });
-} ANS_CATCH
-
-int ans_gpu_encode_chunks(ans_gpu_table* gt, const void* syms, int sym_bytes, uint64_t n, uint64_t chunk_len,
-                          uint8_t* out, uint64_t out_cap, uint64_t* offsets, uint64_t* lens, uint64_t* total) try {
-    return ans_gpu_encode_chunks_ex(gt, syms, sym_bytes, n, chunk_len, ANS_GEN_ZEROS, 0, out, out_cap, offsets, lens,
-                                    total);
-} ANS_CATCH
-
-int ans_gpu_decode_chunks_ex(ans_gpu_table* gt, const uint8_t* in, uint64_t in_len, const uint64_t* offsets,
-                             const uint64_t* lens, uint64_t n, uint64_t chunk_len, int gen_kind, uint64_t seed,
-                             void* out, int sym_bytes) try {
-    (void)hipGetLastError();  // drop a stale error another caller left on this thread
-    if (!gt || !valid_width_u32(sym_bytes) || chunk_len == 0) return ANS_E_ARG;
-    const uint64_t nchunks = (n + chunk_len - 1) / chunk_len;
-    if (nchunks && (!in || !offsets || !lens || !out)) return ANS_E_ARG;
-    if (!valid_kind(gen_kind)) return ANS_E_ARG;
-    if (gt->ts64)
-        return ans_tableset_host_decode(gt->ts64, in, in_len, offsets, lens, n, chunk_len, nullptr, nchunks, gen_kind,
-                                        seed, out, sym_bytes);
-    const fast::ChunkInit ini{gen_kind, seed};
-    if ((sym_bytes == 1 && gt->t.nsym > 256) || (sym_bytes == 2 && gt->t.nsym > 65536)) return ANS_E_ARG;
-    std::vector<uint32_t> l32;
-    uint64_t slot_cap = 0, max_len = 0;
-    int rc = narrow_lens(offsets, lens, nchunks, in_len, l32, &max_len);
-    if (rc) return rc;
-    // The fast decoders read the container in place (any stream alignment); slot_cap (widened
-    // if a possibly corrupt stream is longer than a valid one can be) sizes the pipeline's
-    // batches and tells a dense container from a scattered one.
-    ans_gpu_slot_capacity(gt, chunk_len, &slot_cap);
-    slot_cap = std::max<uint64_t>(slot_cap, (max_len + 64 + 127) & ~uint64_t(127));
-    HIP_TRY(hipSetDevice(gt->g->device));
-    if (nchunks) {  // dense containers (the encoder's output) take the pipelined path
-        uint8_t* in_dev = pipe_kernel_copies() ? mapped_ptr(in) : nullptr;
-        uint8_t* out_dev = in_dev ? mapped_ptr(out) : nullptr;
-        if (in_dev && out_dev) {
-            rc = with_sym_type(sym_bytes, [&](auto t) {
-                return pipe_decode_mapped<decltype(t)>(gt, in_dev, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind,
-                                                       out_dev, ini);
-            });
-            if (rc != kPipeScattered) return rc;
-        }
-        rc = with_sym_type(sym_bytes, [&](auto t) {
-            return pipe_decode<decltype(t)>(gt, in, offsets, l32.data(), slot_cap, n, chunk_len, gen_kind, out,
-                                            ini);
-        });
-        if (rc != kPipeScattered) return rc;
-    }
-    // streams scattered over the buffer: one upload of the whole input, decoded in place
-    const hipStream_t s = gt->g->stream;
-    DevStreams d;
-    DevBuf d_out;
-    if ((rc = upload_streams(in, in_len, offsets, l32, s, d))) return rc;
-    HIP_TRY(d_out.alloc(n * sym_bytes));
-    rc = ans_dev_decode_chunks_ex(gt, d.in.as<uint8_t>(), d.offs.as<uint64_t>(), slot_cap, d.lens.as<uint32_t>(), n,
-                                  chunk_len, gen_kind, seed, d_out.p, sym_bytes, d.status.as<uint32_t>(), s);
-    if (rc || (rc = read_status(gt->g, d.status.as<uint32_t>(), s))) return rc;
-    if (n) HIP_TRY(hipMemcpy(out, d_out.p, n * sym_bytes, hipMemcpyDeviceToHost));
-    return ANS_OK;
-} ANS_CATCH
-
-int ans_gpu_decode_chunks(ans_gpu_table* gt, const uint8_t* in, uint64_t in_len, const uint64_t* offsets,
-                          const uint64_t* lens, uint64_t n, uint64_t chunk_len, int gen_kind, void* out,
-                          int sym_bytes) try {
-    if (gen_kind != ANS_GEN_ZEROS && gen_kind != ANS_GEN_EMPTY) return ANS_E_ARG;  // RANDOM needs a seed: _ex
-    return ans_gpu_decode_chunks_ex(gt, in, in_len, offsets, lens, n, chunk_len, gen_kind, 0, out, sym_bytes);
 } ANS_CATCH
 
 }  // extern "C"

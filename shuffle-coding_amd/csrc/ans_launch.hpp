@@ -1,6 +1,7 @@
 // ans_launch.hpp — the per-symbol-width launchers of the bulk kernels (ans_launch_impl.hpp),
 // explicitly instantiated for u8 / u16 / u32 symbols in ans_launch_{enc,dec}_u*.hip so the
-// kernel instantiations compile in parallel translation units; called by ans_kernels.hip.
+// kernel instantiations compile in parallel translation units; called by ans_kernels.hip (the
+// device-API entries) and ans_pipe.hip (the host-buffer pipeline).
 #pragma once
 
 #include "ans_ctx.hpp"

@@ -1,5 +1,5 @@
 // ans_scan.hpp — the single-workgroup exclusive scan shared by the host-buffer pipeline
-// (ans_kernels.hip) and the edge-list compaction (ans_graph.hip).
+// (ans_pipe.hip) and the edge-list compaction (ans_graph.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

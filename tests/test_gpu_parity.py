@@ -518,14 +518,12 @@ def test_host_pipeline_errors_and_scattered_container():
     assert e.value.code == A.ANS_E_MISMATCH
 
 
-@pytest.mark.parametrize("engine", ["runtime", "kernel"])
 @pytest.mark.parametrize("sym_bytes,batch_bytes,skew", [(1, 1 << 20, 0), (2, 3 << 19, 0), (1, 4096 * 7, 3),
                                                        (2, 1 << 20, 5)])
-def test_host_pipeline_page_locked(sym_bytes, batch_bytes, skew, engine, monkeypatch):
-    """Page-locked (ans_host_alloc) buffers: asynchronous runtime copies (default), or with
-    ANS_PIPE_COPY=kernel the device-driven path (copy kernels over PCIe, the container offset
-    carried on the device).  `skew` shifts every buffer off 16-byte alignment."""
-    monkeypatch.setenv("ANS_PIPE_COPY", engine)
+def test_host_pipeline_page_locked(sym_bytes, batch_bytes, skew):
+    """Page-locked (ans_host_alloc) buffers take the same pipeline as pageable ones; the
+    runtime's copies from and into them run asynchronously.  `skew` shifts every buffer off
+    16-byte alignment."""
     g = A.Gpu(0)
     g.set_batch_bytes(batch_bytes)
     masses = A.c3_masses()
@@ -555,11 +553,70 @@ def test_host_pipeline_page_locked(sym_bytes, batch_bytes, skew, engine, monkeyp
     rc = A.lib().ans_gpu_encode_chunks(gt.h, A._np_ptr(syms), sym_bytes, n, L, A._np_ptr(out), total.value - 1,
                                        A._np_ptr(offsets), A._np_ptr(lens), A.ctypes.byref(total))
     assert rc == A.ANS_E_LEN and total.value == len(odata)
-    # corruption in a middle batch is reported through the mapped path too
+    # corruption in a middle batch is reported with page-locked buffers too
     out[int(ooffsets[nchunks // 2]) + 2] ^= 0x41
     rc = A.lib().ans_gpu_decode_chunks(gt.h, A._np_ptr(out), len(odata), A._np_ptr(offsets), A._np_ptr(lens),
                                        n, L, A.GEN_ZEROS, A._np_ptr(back), sym_bytes)
     assert rc == A.ANS_E_MISMATCH
+
+
+@pytest.mark.parametrize("kind,seed", [(A.GEN_ZEROS, 0), (A.GEN_RANDOM, 5)], ids=["zeros", "random5"])
+@pytest.mark.parametrize("n", [39 * 4096, 40 * 4096 + 777, 2 * 4096 + 5])
+@pytest.mark.parametrize("sym_bytes", [1, 2])
+def test_host_pipeline_initial_messages_across_batches(sym_bytes, n, kind, seed, monkeypatch):
+    """Batch b starts its chunks at Message::random(seed + c0), c0 its first chunk: with 3 chunks
+    per batch and the default six slots, 13 full batches, 14 batches with a short last one and a
+    ragged last chunk (every slot used more than twice), and a single batch must all give the
+    oracle's container, decode losslessly, and end elsewhere under another seed."""
+    monkeypatch.delenv("ANS_PIPE_DEPTH", raising=False)
+    L = 4096
+    g = A.Gpu(0)
+    g.set_batch_bytes(3 * L * sym_bytes)
+    masses = A.c3_masses()
+    gt = A.GpuTable(g, A.Categorical(masses))
+    dtype = {1: np.uint8, 2: np.uint16}[sym_bytes]
+    syms = orc.gen_iid(masses, 21, 0, n).astype(dtype)
+    data, offsets, lens = gt.encode_chunks(syms, L, gen_kind=kind, seed=seed)
+    assert g.pipe_depth() == 6
+    okind = orc.RANDOM if kind == A.GEN_RANDOM else orc.ZEROS
+    od, oo, ol = orc.encode_chunks(masses, syms.astype(np.uint32), L, kind=okind, seed=seed)
+    assert np.array_equal(offsets, oo) and np.array_equal(lens, ol)
+    assert data.tobytes() == od.tobytes()
+    back = gt.decode_chunks(data, offsets, lens, n, L, dtype, gen_kind=kind, seed=seed)
+    assert np.array_equal(back, syms)
+    if kind == A.GEN_RANDOM:
+        with pytest.raises(A.AnsError) as e:  # another seed's initial messages are not where decoding ends
+            gt.decode_chunks(data, offsets, lens, n, L, dtype, gen_kind=kind, seed=seed + 1)
+        assert e.value.code == A.ANS_E_MISMATCH
+
+
+def test_host_pipeline_workspace_after_a_reported_error():
+    """A symbol outside the table in a middle batch: the call reports what a one-batch call on a
+    fresh context reports, and the workspace it leaves codes the next calls correctly."""
+    L, n = 4096, 40 * 4096 + 777
+    masses = A.c3_masses()
+    syms = orc.gen_iid(masses, 23, 0, n).astype(np.uint16)
+    bad = syms.copy()
+    bad[20 * L + 123] = 300  # chunk 20: in the seventh of 14 batches
+
+    def failing_encode(g):
+        gt = A.GpuTable(g, A.Categorical(masses))
+        with pytest.raises(A.AnsError) as e:
+            gt.encode_chunks(bad, L)
+        return gt, e.value.code
+
+    g1 = A.Gpu(0)  # the default batch size: one batch
+    _, want = failing_encode(g1)
+    g = A.Gpu(0)
+    g.set_batch_bytes(3 * L * 2)
+    gt, got = failing_encode(g)
+    assert got == want
+    data, offsets, lens = gt.encode_chunks(syms, L)
+    od, oo, ol = orc.encode_chunks(masses, syms.astype(np.uint32), L)
+    assert np.array_equal(offsets, oo) and np.array_equal(lens, ol)
+    assert data.tobytes() == od.tobytes()
+    back = gt.decode_chunks(data, offsets, lens, n, L, np.uint16)
+    assert np.array_equal(back, syms)
 
 
 # ---------------------------------------------------------------- Codec::samples in bulk

@@ -86,6 +86,8 @@ def test_every_gpu_entry_is_exception_guarded():
                     unguarded.append(f"{fn}:{m.group(1)}")
         if fn in ("ans_kernels.hip", "ans_codecs.hip", "ans_graph.hip"):
             assert n_defs >= 9, fn
+        if fn == "ans_pipe.hip":  # the host-buffer entries: alloc / free, batch bytes, depth, the four chunk calls
+            assert n_defs >= 8, fn
     assert not unguarded, unguarded
 
 
