@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <utility>
 
+#include "ans_dec_u.hpp"
 #include "ans_renorm.hpp"
 #include "ans_table.hpp"
 
@@ -66,18 +67,18 @@ static_assert(kDecRowOff + 8 * 257 <= kDecTableBytes, "row decode tables fit");
 // the fix-up-free decoder's LDS layout (k_decode kMode = kModeU, FastTable::dec_u): the quotient
 // from below (q_m in {q - 1, q}) leaves u = head - q_m * norm in [0, 2 norm), which indexes a
 // virtual alphabet of 512 symbols: v < 256 is symbol v at cdf(v) (q = q_m), v >= 256 symbol
-// v - 256 at norm + cdf(v - 256) (q = q_m + 1).  Buckets of u (width 2^us) as 8-B threshold
-// pairs, then 512 rows (cum_row, p) with head = p * q_m + (u - cum_row).  A bucket at a = j << us
-// holds, for its boundaries c = cdfv(s0+1) and cdfv(s0+2) (s0 = the virtual symbol at a), the
-// word (j & 1) << 31 | ((min(c - a, 2^us) - 1) << (31 - us)) | s0: u's offset in the bucket
-// shifted up to bit 30 under the bucket index's low bit; rx = u << (31 - us) (mod 2^32) holds the
-// same bit 31 and exceeds the word exactly when u >= c (its low bits are zero, the word's are
-// s0).  The two differ by less than 2^31, so [rx > w] is the sign bit of w - rx, and
-// s = w1 + ((w1 - rx) >> 31) + ((w2 - rx) >> 31) in its low bits: two v_sub, two v_lshrrev and
-// a v_add3 (r06, 14.2 issue cycles; two v_cmp / v_addc pairs took 19.1 with their vcc hazards),
-// on w1 itself, with no separate s0 array (one random LDS read fewer per symbol).  The bits of
-// w1 above s0 start at bit 31 - us >= 13 and leave the row address ((s << 3) mod 2^16) alone:
-// us <= 18 (norm up to 3,072 * 2^17 = 402,653,184; wider tables keep the row decoder).
+// v - 256 at norm + cdf(v - 256) (q = q_m + 1).  Buckets of u (width 2^us) as 8-B word pairs,
+// then 512 rows (cum_row, p) with head = p * q_m + (u - cum_row).  A bucket at a = j << us
+// holds, for its boundaries c_i = cdfv(s0 + i), i = 1, 2 (s0 = the virtual symbol at a), the
+// additive words of ans_dec_u.hpp: k1 = ((s0 + 1) << us) - a - rel_1, k2 = (1 << us) - a - rel_2
+// with rel_i = min(c_i - a, 2^us).  u + k_i = (e_i << us) + (2^us + (u - a) - rel_i), e_1 = s0,
+// e_2 = 0: the second term is below 2^(us+1) and its bit us is [u >= c_i].  So
+// v = (u + k1 + ((u + k2) & 2^us)) >> us: v_add, v_and, v_add3, v_lshrrev (the mask and us in
+// SGPRs), then v_lshlrev_b16 for the row address: five VALU where the threshold words of r06
+// (rx = u << (31 - us), two v_sub, two sign-bit shifts, v_add3, row shift) took seven, and v is
+// clean: no bits above the symbol.  s0 rides in k1 (no separate s0 array: one random LDS read
+// fewer per symbol).  (s0 + 3) << us <= 2^32 keeps the sum in 32 bits: us <= 18 (norm up to
+// 3,072 * 2^17 = 402,653,184; wider tables keep the row decoder).
 constexpr uint32_t kDecUNbMax = (kDecTableBytes - 8 * 512) / 8;
 constexpr uint32_t kDecURowOff = 8 * kDecUNbMax;
 constexpr uint32_t kDecUShiftMax = 18;
@@ -1044,25 +1045,28 @@ struct DecChain {
             asm("v_fma_f64 %0, %1, %2, %3" : "=v"(tq) : "v"(xd), "s"(rcp8), "v"(magic));
         }
         const uint64_t raw = static_cast<uint64_t>(__double_as_longlong(tq));  // q_m + 0x43000000'00000000
-        cf = lo32(head) - lo32(raw) * norm;            // u (src/ans.rs:110-111 before the split)
+        // u = lo32(head) - lo32(q_m) norm (src/ans.rs:110-111 before the split) as the low word of
+        // lo32(q_m) (2^32 - norm) + head: one v_mad_u64_u32 with the negated norm in an SGPR where
+        // v_mul_lo_u32 and v_sub took two issues (through asm, so that the form holds although only
+        // the low word is read; decode -2.4% in a same-box A/B)
+        {
+            uint64_t m;
+            asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(m) : "v"(lo32(raw)), "s"(0u - norm), "v"(head) : "vcc");
+            cf = lo32(m);
+        }
         // (kNormSmall: + qh in the high word, q_m = qh 2^32 + the estimate)
         const uint32_t hw = kNR == kNormSmall ? hi32(raw) + qh : hi32(raw);
         if constexpr (kP24) qq = mk64(hw, lo32(raw));  // (low 24 bits: hi32(q_m) < 2^24)
         else qq = mk64(hw - 0x43000000u, lo32(raw));   // q_m < 2^52 (+ qh 2^32)
     }
-    // the u-domain icdf: bucket u >> shift -> threshold words (w1, w2) with s0 in w1's low bits
-    // (kDecUNbMax), the virtual symbol v = s0 + [rx > w1] + [rx > w2] for rx = u << rshift
-    // (rshift = 31 - shift: rx and the words agree in bit 31, so each test is a sign bit), then its
-    // row (cum_row, p); only v's low 13 bits reach the row address
-    __device__ __forceinline__ void lookup_u(uint32_t shift, uint32_t rshift) {
+    // the u-domain icdf: bucket u >> shift -> additive words (k1, k2) (kDecUNbMax, ans_dec_u.hpp),
+    // the virtual symbol v = s0 + [u >= c1] + [u >= c2] as (u + k1 + ((u + k2) & 2^shift)) >> shift,
+    // then its row (cum_row, p); v is clean (below 512), so its low byte is the symbol
+    __device__ __forceinline__ void lookup_u(uint32_t shift) {
         const uint32_t bi = cf >> shift;
         const uint64_t cc = lds_ld64(shl16<3>(bi));  // bi < kDecUNbMax
-        const uint32_t rx = cf << rshift;
-        const uint32_t w1 = lo32(cc), w2 = hi32(cc);
-        asm volatile("v_add3_u32 %0, %1, %2, %3"
-                     : "=v"(sx)
-                     : "v"(w1), "v"((w1 - rx) >> 31), "v"((w2 - rx) >> 31));
-        const uint64_t row = lds_ld64(kDecURowOff + shl16<3>(sx));  // (sx mod 2^13) < 512
+        sx = dec_u_pick(cf, lo32(cc), hi32(cc), shift);
+        const uint64_t row = lds_ld64(kDecURowOff + shl16<3>(sx));  // sx < 512
         cum = lo32(row);
         nxt = hi32(row);  // pmf(s)
         far = false;
@@ -1279,7 +1283,7 @@ __global__ __launch_bounds__(kDecBlock, 4) void k_decode(FastTable t, const uint
                                 asm("v_max3_u32 %0, %1, %2, %3" : "=v"(hmax) : "v"(hmax), "v"(hodd), "v"(hi32(ch.head)));
                             }
                         }
-                        ch.lookup_u(shift, 31u - shift);
+                        ch.lookup_u(shift);
                         __builtin_amdgcn_s_setprio(0);
                     } else {
                         ch.template renorm_div<kJ4, kNR>(L, hL8, norm, rcp_norm, neg_norm);
@@ -1304,7 +1308,7 @@ __global__ __launch_bounds__(kDecBlock, 4) void k_decode(FastTable t, const uint
 #pragma unroll
                         for (int j = 0; j < U; ++j) {
                             ch.template renorm_div_u<kJ4, kNR, kP24, true>(L, hL8, norm, rcp_norm, rcp8, magic_u, neg_norm);
-                            ch.lookup_u(shift, 31u - shift);
+                            ch.lookup_u(shift);
                             ch.template update<kP24, kRows>();
                             sv[j] = ch.sx;
                             if constexpr (kPack4) {

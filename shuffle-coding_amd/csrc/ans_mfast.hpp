@@ -915,11 +915,12 @@ struct NoState {
 // constant 0xFFFFFF00 for every table (r05: one ds_read_b128 per pop where a 32-B header took
 // two; the decoder is LDS-bound), the (cdf(s), pmf(s)) rows of every table at
 // kIndRowOff + 8 (t*257 + s), then each table's icdf
-// buckets of width 2^us (ans_fast.hpp kModeU's folded words): bucket j at a = j << us holds
-// w1 = ((min(cdf(s0+1) - a, 2^us) - 1) << rshift) | s0 and w2 the same for cdf(s0+2) (where
-// cdf(s0+3) still lies inside the bucket, cf beyond s0+2 shows as cf - cdf(s) >= pmf(s) on the
-// row and takes a voted scan of the rows).  rshift = 32 - us >= 10 keeps the 9-bit symbol clear,
-// so a table of norm 2^31 needs only 512 buckets.
+// buckets of width 2^us (ans_dec_u.hpp's additive words, as ans_fast.hpp kModeU): bucket j at
+// a = j << us holds k1 = dec_u_word(a, cdf(s0+1), s0, us) and k2 = dec_u_word(a, cdf(s0+2), 0, us),
+// and s = ((cf + k1) >> us) + ((cf + k2) >> us) (where cdf(s0+3) still lies inside the bucket, cf
+// beyond s0+2 shows as cf - cdf(s) >= pmf(s) on the row and takes a voted scan of the rows).
+// (s0 + 2) << us < 2^32 for s0 <= 255 keeps the sums in 32 bits up to us = 22, so a table of
+// norm 2^31 needs only 512 buckets.
 constexpr uint32_t kIndMaxTables = 15;                  // 16 (257 t + s) < 2^16
 constexpr uint32_t kIndHdrBytes = 16;                   // decoder header per table at kIndHdrBytes t
 constexpr uint32_t kIndLOff = 256;                      // L_t at kIndLOff + 8 t (the renorm's rare path)
@@ -929,7 +930,7 @@ constexpr uint32_t kIndRowShift = 19;
 static_assert(kIndHdrBytes * kIndMaxTables <= kIndLOff && kIndLOff + 8 * kIndMaxTables <= kIndRowOff, "header area");
 static_assert(257 * (kIndMaxTables - 1) < (1u << (32 - kIndRowShift)), "row index field");
 constexpr uint32_t kScreenAll = 0xFFFFFF00u;  // hi32(L) << 8 >= this for every norm < 2^32 (L > 2^56 - 2^32)
-constexpr uint32_t kIndMaxShift = 22;                   // rshift = 32 - us >= 10
+constexpr uint32_t kIndMaxShift = 22;                   // (255 + 2) << us < 2^32
 
 // kNR (ans_fast.hpp kNormStd / kNormSmall / kNormBig): every table of the set in that norm range;
 // kNormSmall rows carry 1/p rounded up and the headers 1/norm rounded up (the long division).
@@ -1091,21 +1092,12 @@ struct IndepModel {
         asm("v_add_lshl_u32 %0, %1, %2, 3" : "=v"(ba) : "v"(cf >> hw), "v"(__builtin_amdgcn_ubfe(hw, kIndBktShift, kIndRowShift - kIndBktShift)));
         const uint64_t cc = lds_ld64(kTab + ba);
         __builtin_amdgcn_s_setprio(0);
-        // rx = cf << (32 - us) as ({cf, 0} >> us): v_alignbit takes us from the header word's low
-        // five bits as they are (no unpacking of 32 - us)
-        const uint32_t rx = __builtin_amdgcn_alignbit(cf, 0u, hw);
-        uint32_t sx;
-        asm volatile(
-            "v_cmp_gt_u32 vcc, %[rx], %[w1]\n\t"
-            "s_nop 1\n\t"
-            "v_addc_co_u32 %[sx], vcc, 0, %[w1], vcc\n\t"
-            "v_cmp_gt_u32 vcc, %[rx], %[w2]\n\t"
-            "s_nop 1\n\t"
-            "v_addc_co_u32 %[sx], vcc, 0, %[sx], vcc"
-            : [sx] "=&v"(sx)
-            : [rx] "v"(rx), [w1] "v"(lo32(cc)), [w2] "v"(hi32(cc))
-            : "vcc");
-        sx &= 0x1FFu;  // the symbol (w1's threshold bits above it dropped)
+        // the additive words (ans_dec_u.hpp): (cf + k1) >> us = s0 + [cf >= cdf(s0+1)] and
+        // (cf + k2) >> us = [cf >= cdf(s0+2)]; v_lshrrev takes us from the header word's low five
+        // bits as they are.  Two adds, two shifts and the sum, where the threshold words took a
+        // v_alignbit, two v_cmp / v_addc pairs through vcc and a mask
+        uint32_t sx = fast::dec_u_pick2(cf, lo32(cc), hi32(cc), hw & 31u);
+        asm volatile("" : "+v"(sx));  // (the sum stays one value: it is the symbol returned)
         const uint32_t r257 = hw >> kIndRowShift;  // 257 t: the table's first row
         uint32_t ra;
         asm("v_add_lshl_u32 %0, %1, %2, 3" : "=v"(ra) : "v"(sx), "v"(r257));

@@ -28,6 +28,7 @@ COST = {
     "v_lshl_or_b32": 4.32, "v_bfe_u32": 4.18, "v_mad_u32_u24": 4.42, "v_ffbh_u32": 4.10, "v_min_u32": 4.29,
     "v_max_u32": 4.18, "v_cndmask_b32": 4.57, "v_cmp": 4.77, "v_add_co_u32": 4.83, "v_addc_co_u32": 4.80,
     "v_sub_co_u32": 4.61, "v_and_or_b32": 4.39, "v_or3_b32": 4.27, "v_bfi_b32": 4.28, "v_lshl_add_u32": 4.41,
+    "v_add_lshl_u32": 4.20,  # r12 (tools/microbench.hip, profiles/r12_valu_microbench.txt)
     "v_rcp_f64": 16.31, "v_mov_b32": 2.4, "v_mov_b64": 4.8,
 }
 

@@ -177,6 +177,10 @@ KERNEL(k_and_or_b32, DECL32, INIT32, OP3("v_and_or_b32"), SINK32)
 KERNEL(k_or3_b32, DECL32, INIT32, OP3("v_or3_b32"), SINK32)
 KERNEL(k_bfi_b32, DECL32, INIT32, OP3("v_bfi_b32"), SINK32)
 KERNEL(k_lshl_add_u32, DECL32, INIT32, OP3("v_lshl_add_u32"), SINK32)
+// (a + b) << 3, the shift an inline constant as the decoders' row addresses use it
+#define ADDLSHL(D, S) asm volatile("v_add_lshl_u32 %0, %0, %1, 3" : "+v"(D) : "v"(S))
+#define OPADDLSHL ADDLSHL(a0, a1); ADDLSHL(a1, a2); ADDLSHL(a2, a3); ADDLSHL(a3, a4); ADDLSHL(a4, a5); ADDLSHL(a5, a6); ADDLSHL(a6, a7); ADDLSHL(a7, a0)
+KERNEL(k_add_lshl_u32, DECL32, INIT32, OPADDLSHL, SINK32)
 KERNEL(k_fma_f32_dep, DECLS, INITS, OPFMA32DEP, SINKS)
 KERNEL(k_add_u32_dep, DECL32, INIT32, OPADDDEP, SINK32)
 KERNEL(k_mad64_dep, DECL64, INIT64, OPMADDEP, SINK64)
@@ -228,6 +232,7 @@ int main(int argc, char** argv) {
         {"v_cmp_gt_u32_e32", k_cmp_e32, 1}, {"v_add_co_u32", k_add_co, 1}, {"v_addc_co_u32", k_addc_co, 1},
         {"v_sub_f32_e64", k_sub_f32_e64, 1}, {"v_add_u32_e64", k_add_u32_e64, 1}, {"v_and_or_b32", k_and_or_b32, 1},
         {"v_or3_b32", k_or3_b32, 1}, {"v_bfi_b32", k_bfi_b32, 1}, {"v_lshl_add_u32", k_lshl_add_u32, 1},
+        {"v_add_lshl_u32", k_add_lshl_u32, 1},
         {"DEP v_fma_f32", k_fma_f32_dep, 1}, {"DEP v_add_u32", k_add_u32_dep, 1}, {"DEP v_mad_u64_u32", k_mad64_dep, 1},
         {"DEP v_fma_f64", k_fma_f64_dep, 1}, {"DEP v_perm_b32", k_perm_dep, 1},
         {"v_rcp_f64", k_rcp_f64, 1}, {"v_frexp_exp_i32_f64", k_frexp, 1}, {"v_sub_co_u32", k_sub_co, 1},
