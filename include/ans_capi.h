@@ -104,6 +104,24 @@ int ans_cat_pop(ans_msg *m, const ans_table *t, uint64_t *x);
 /* IID::push (reverse order) / IID::pop (forward)  src/codec.rs:415-424 */
 int ans_push_iid(ans_msg *m, const ans_table *t, const uint32_t *syms, size_t n);
 int ans_pop_iid(ans_msg *m, const ans_table *t, uint32_t *out, size_t n);
+/* Recursive multiset shuffle coding of n values of the table's alphabet as ONE multiset:
+ * ShuffleCodec<IIDVecSliceCodecs<Categorical>, VecOrbitCodecs>  src/recursive/mod.rs:117-148,
+ * src/recursive/multiset.rs:13-91,139-141 (the harness's iid_multiset_shuffle_codec).
+ *   push: the order of syms does not matter.  For L = n .. 1: a value's orbit is POPPED under the
+ *         orbit distribution of the L values left (a MutCategorical keyed by orbit id,
+ *         src/codec.rs:145-181: norm L, pmf = how many of them are that value, orbits in ascending
+ *         id order), the value leaves the multiset and is pushed under the table.
+ *   pop:  for k = 0 .. n-1: a value is popped under the table, joins the multiset, and its orbit is
+ *         PUSHED under the orbit distribution of the k + 1 values so far.  out receives the values
+ *         in pop order (the reference wraps them as Unordered); that order is deterministic.
+ * ans_orbit_id(x) is the orbit id of value x: hash(x) of src/recursive/prefix_orbit.rs:132-136,
+ * std's DefaultHasher (SipHash-1-3, keys 0, 0) over the usize's 8 little-endian bytes.
+ * Errors as ans_cat_push / ans_cat_pop (ANS_E_SYMBOL, ANS_E_ZERO_MASS, ANS_E_EXHAUSTED); a table
+ * of more than 65,536 symbols, or one in which two symbols share an orbit id, is ANS_E_ARG.
+ * Any message, any tail generator.  It saves log2(n! / prod multiplicity!) bits over ans_push_iid. */
+uint64_t ans_orbit_id(uint64_t x);
+int ans_mset_push(ans_msg *m, const ans_table *t, const uint32_t *syms, size_t n);
+int ans_mset_pop(ans_msg *m, const ans_table *t, uint32_t *out, size_t n);
 
 /* ======================================================================
  * (4) GPU bulk path (MI355X / gfx950) — the data-parallel hot path.
@@ -160,9 +178,10 @@ int ans_gpu_table_paths(const ans_gpu_table *gt, uint32_t *paths);
  *   k_decode_g<u16,nr=std>   k_decode_generic<u8,lds=1,fast=1>
  *   k_menc<indep,u8,spp=16,lanes=256,res=0,rare=0,nr=std>   k_mdec<indep,u8,spp=16,lanes=256,res=0,lean=1,nr=std>
  *   k_encode64<catset,u8>   k_decode64<catset,u8>   k_push64<u8>   k_pop64<u8>
+ *   k_mset_push<u8,cnt=lds>   k_mset_pop<u16,cnt=global>      (cnt: where the per-lane counts live)
  * The calls that write it are the Categorical table's (sections 3 and 4: fixed, ragged and variable
- * chunks, host or device buffers; a pipelined host call leaves its last batch's launches) and the
- * Independent ones (new messages and resume); helper kernels (staging, compaction) are not named,
+ * chunks, host or device buffers; a pipelined host call leaves its last batch's launches), the
+ * Independent ones (new messages and resume) and the multiset ones; helper kernels (staging, compaction) are not named,
  * and the other calls (and calls that return before any launch: no symbols, bad arguments) leave
  * the record as it was.  Empty before the first such call.
  * Writes *len = the text's bytes (without the terminating NUL) and, if cap > *len, the
@@ -475,6 +494,59 @@ int ans_gpu_independent_pop_var_chunks(ans_gpu_tableset *ts, const uint32_t *tab
                                        uint64_t nchunks, const uint64_t *starts, void *out_syms, int sym_bytes,
                                        uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
                                        uint64_t *total);
+
+/* Multisets in bulk: ans_mset_push / ans_mset_pop (section 3) of chunk c's symbols as one multiset
+ * onto / from the message ALREADY in slot c, one lane per chunk, under the resume contract above word
+ * for word: the input is Message::unflatten(slot bytes, d_lens[c]) with the Empty tail, the result is
+ * flattened back into the slot and d_lens[c] is its length (a chunk of zero symbols grows by the one
+ * 0x00 of flatten); a pull past the stream's start is ANS_E_EXHAUSTED, a result past slot_cap (or a
+ * d_lens[c] above it) ANS_E_LEN, a symbol outside the alphabet ANS_E_SYMBOL, one of mass 0
+ * ANS_E_ZERO_MASS, each in *d_status with d_lens[c] = 0.  The bytes equal the host codec's.
+ * `table` picks the set's table (its alphabet: at most 65,536 symbols, else ANS_E_ARG); sym_bytes is
+ * 1, 2 or 4; a chunk holds fewer than 2^32 symbols.  pop writes chunk c's values in pop order at its
+ * positions of d_syms.
+ * Push needs slot_cap >= d_lens[c] + ans_gpu_tableset_slot_capacity(ts, chunk_len) (the orbit pops
+ * only shrink the message).  A pop ends below where it began, but between two steps the message can
+ * be longer: step k takes a value's bits out and puts up to log2(k + 1) bits of its orbit back.
+ * ans_gpu_mset_pop_slack gives a bound on that growth, (chunk_len / 8 + 1) * ceil(log2(chunk_len + 1))
+ * + 16 bytes: with slot_cap >= d_lens[c] + that, a pop never meets ANS_E_LEN (the longest chunk's
+ * for _var; the host-buffer calls apply it themselves).
+ * The per-lane counts live in LDS as u16 (kernel names k_mset_push<u8,cnt=lds> in ans_gpu_last_launch)
+ * when the alphabet has at most 1,024 symbols and no chunk is longer than 65,535; otherwise, and in
+ * the device-resident _var calls (whose chunk lengths the host does not see), as u32 in a workspace
+ * the context owns (cnt=global), which calls on one context therefore must not share between
+ * streams running at the same time. */
+int ans_gpu_mset_pop_slack(uint64_t chunk_len, uint64_t *bytes);
+int ans_dev_mset_push(ans_gpu_tableset *ts, uint32_t table, const void *d_syms, int sym_bytes, uint64_t n,
+                      uint64_t chunk_len, uint8_t *d_slots, uint64_t slot_cap, uint32_t *d_lens /* in/out */,
+                      uint32_t *d_status, void *stream);
+int ans_dev_mset_pop(ans_gpu_tableset *ts, uint32_t table, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                     uint32_t *d_lens /* in/out */, uint64_t n, uint64_t chunk_len, void *d_syms, int sym_bytes,
+                     uint32_t *d_status, void *stream);
+int ans_dev_mset_push_var(ans_gpu_tableset *ts, uint32_t table, const void *d_syms, int sym_bytes, uint64_t nchunks,
+                          const uint64_t *d_starts, uint8_t *d_slots, uint64_t slot_cap,
+                          uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_mset_pop_var(ans_gpu_tableset *ts, uint32_t table, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                         uint32_t *d_lens /* in/out */, uint64_t nchunks, const uint64_t *d_starts, void *d_syms,
+                         int sym_bytes, uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, a dense container in and one out exactly as the
+ * ans_gpu_independent_push_chunks family (out == NULL is the size query; pop still fills out_syms). */
+int ans_gpu_mset_push_chunks(ans_gpu_tableset *ts, uint32_t table, const void *syms, int sym_bytes, uint64_t n,
+                             uint64_t chunk_len, const uint8_t *in, uint64_t in_len, const uint64_t *in_offsets,
+                             const uint64_t *in_lens, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
+                             uint64_t *lens, uint64_t *total);
+int ans_gpu_mset_pop_chunks(ans_gpu_tableset *ts, uint32_t table, const uint8_t *in, uint64_t in_len,
+                            const uint64_t *in_offsets, const uint64_t *in_lens, uint64_t n, uint64_t chunk_len,
+                            void *out_syms, int sym_bytes, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
+                            uint64_t *lens, uint64_t *total);
+int ans_gpu_mset_push_var_chunks(ans_gpu_tableset *ts, uint32_t table, const void *syms, int sym_bytes,
+                                 uint64_t nchunks, const uint64_t *starts, const uint8_t *in, uint64_t in_len,
+                                 const uint64_t *in_offsets, const uint64_t *in_lens, uint8_t *out, uint64_t out_cap,
+                                 uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_mset_pop_var_chunks(ans_gpu_tableset *ts, uint32_t table, const uint8_t *in, uint64_t in_len,
+                                const uint64_t *in_offsets, const uint64_t *in_lens, uint64_t nchunks,
+                                const uint64_t *starts, void *out_syms, int sym_bytes, uint8_t *out, uint64_t out_cap,
+                                uint64_t *offsets, uint64_t *lens, uint64_t *total);
 
 /* ======================================================================
  * (5) Graph models' bulk-IID caller — DenseSetIID<EdgeIndex, AllEdgeIndices> with an

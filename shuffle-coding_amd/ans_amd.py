@@ -147,6 +147,18 @@ SIGNATURES = {
     "ans_gpu_independent_pop_chunks": (ci, [vp, vp, vp, u64, vp, vp, u64, u64, vp, ci, vp, u64, vp, vp, u64p]),
     "ans_gpu_independent_push_var_chunks": (ci, [vp, vp, vp, ci, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_independent_pop_var_chunks": (ci, [vp, vp, vp, u64, vp, vp, u64, vp, vp, ci, vp, u64, vp, vp, u64p]),
+    "ans_orbit_id": (u64, [u64]),
+    "ans_mset_push": (ci, [vp, vp, vp, sz]),
+    "ans_mset_pop": (ci, [vp, vp, vp, sz]),
+    "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
+    "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
+    "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
+    "ans_dev_mset_push_var": (ci, [vp, ctypes.c_uint32, vp, ci, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_mset_pop_var": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, vp, vp, ci, vp, vp]),
+    "ans_gpu_mset_push_chunks": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_mset_pop_chunks": (ci, [vp, ctypes.c_uint32, vp, u64, vp, vp, u64, u64, vp, ci, vp, u64, vp, vp, u64p]),
+    "ans_gpu_mset_push_var_chunks": (ci, [vp, ctypes.c_uint32, vp, ci, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_mset_pop_var_chunks": (ci, [vp, ctypes.c_uint32, vp, u64, vp, vp, u64, vp, vp, ci, vp, u64, vp, vp, u64p]),
     "ans_gpu_graphs_encode": (ci, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ci, ci, u64, vp, vp, vp, vp,
                                    vp, ci, u64, vp, u64, vp, vp, u64p]),
     "ans_gpu_graphs_decode": (ci, [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ci, ci, u64, vp, vp, u64, vp,
@@ -578,6 +590,61 @@ class Independent(Codec):  # src/codec.rs:366-403
                 return None
             total += b
         return total
+
+
+class Unordered(list):
+    """A multiset's values in some order (the reference's Unordered): equal to any list of the same
+    values whatever their order."""
+
+    def __eq__(self, other):
+        try:
+            return sorted(self) == sorted(other)
+        except TypeError:
+            return NotImplemented
+
+    def __ne__(self, other):
+        eq = self.__eq__(other)
+        return eq if eq is NotImplemented else not eq
+
+    __hash__ = None
+
+
+def orbit_id(x):
+    """hash(x) of src/recursive/prefix_orbit.rs:132-136 (SipHash-1-3, keys 0, 0, of the usize)."""
+    return int(lib().ans_orbit_id(int(x)))
+
+
+class MultisetShuffle(Codec):
+    """Recursive shuffle coding of a multiset of `length` values of a Categorical's alphabet:
+    ShuffleCodec<IIDVecSliceCodecs<Categorical>, VecOrbitCodecs> (src/recursive/mod.rs:117-148,
+    src/recursive/multiset.rs:139-141), on the host through ans_mset_push / ans_mset_pop.  pop
+    returns the values in the codec's pop order as an Unordered."""
+
+    def __init__(self, item, length):
+        if not isinstance(item, Categorical):
+            raise AnsError(ANS_E_ARG, "MultisetShuffle: the item codec must be a Categorical")
+        self.item = item
+        self.len = length
+
+    def push(self, m, x):
+        assert len(x) == self.len
+        s = np.ascontiguousarray(np.asarray(x, dtype=np.uint32))
+        _check(lib().ans_mset_push(m.h, self.item.table, _np_ptr(s), len(s)), "MultisetShuffle::push")
+
+    def pop(self, m):
+        out = np.zeros(max(self.len, 1), np.uint32)
+        _check(lib().ans_mset_pop(m.h, self.item.table, _np_ptr(out), self.len), "MultisetShuffle::pop")
+        return Unordered(int(v) for v in out[:self.len])
+
+    def bits(self, x):
+        """IID's bits less the order's: log2(n! / prod multiplicity!)."""
+        import math
+        total = IID(self.item, len(x)).bits(x)
+        if total is None:
+            return None
+        _, mult = np.unique(np.asarray(x, dtype=np.uint64), return_counts=True)
+        order = math.lgamma(len(x) + 1) - sum(math.lgamma(int(c) + 1) for c in mult)
+        return total - order / math.log(2)
 
 
 # ============================================================== GPU bulk path (section 4)
@@ -1095,6 +1162,92 @@ class GpuTableSet:
         _check(lib().ans_dev_independent_pop(self.h, _dptr(d_tids), _dptr(d_slots), slot_cap, _dptr(d_lens), n,
                                              chunk_len, _dptr(d_syms), sym_bytes, _dptr(d_status), _sptr(stream)),
                "ans_dev_independent_pop")
+
+    # ---- multisets in bulk (include/ans_capi.h 4b): chunk c's symbols as ONE multiset onto / from
+    # message c, by recursive shuffle coding with table `table` of the set (MultisetShuffle per chunk)
+    @staticmethod
+    def mset_pop_slack(chunk_len):
+        """Bytes a message can grow by during a pop of chunk_len values (slot_cap of dev_mset_pop)."""
+        b = u64(0)
+        _check(lib().ans_gpu_mset_pop_slack(chunk_len, ctypes.byref(b)), "ans_gpu_mset_pop_slack")
+        return b.value
+
+    def _mset_push(self, where, fn, table, syms, shape_args, nchunks, longest, data, offsets, lens):
+        syms = np.ascontiguousarray(syms)
+        if syms.ndim != 1 or syms.dtype not in _WIDTH or _WIDTH[syms.dtype] > 4:
+            raise AnsError(ANS_E_ARG, f"{where}: symbols must be one array of u8, u16 or u32")
+        data, offsets, lens = self._resume_container(where, data, offsets, lens, nchunks)
+        cap = data.size + nchunks * self.slot_capacity(max(longest, 1))
+        return self._resume_call(where, fn, (table, _np_ptr(syms), _WIDTH[syms.dtype]) + shape_args,
+                                 (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens)),
+                                 nchunks, cap)
+
+    def _mset_pop(self, where, fn, table, n, shape_args, nchunks, data, offsets, lens, dtype):
+        if np.dtype(dtype) not in _WIDTH or _WIDTH[np.dtype(dtype)] > 4:
+            raise AnsError(ANS_E_ARG, f"{where}: symbols are u8, u16 or u32")
+        data, offsets, lens = self._resume_container(where, data, offsets, lens, nchunks)
+        syms = np.zeros(max(n, 1), dtype)
+        container = self._resume_call(
+            where, fn, (table, _np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens)),
+            shape_args + (_np_ptr(syms), _WIDTH[np.dtype(dtype)]), nchunks, data.size + 16 * nchunks)
+        return syms[:n], container
+
+    def mset_push_chunks(self, table, syms, chunk_len, data, offsets, lens):
+        """MultisetShuffle::push of chunk c's symbols [c*chunk_len, ...) onto message c of the
+        container (data, offsets, lens), then flatten: returns the container of the results."""
+        if chunk_len <= 0:
+            raise AnsError(ANS_E_ARG, "mset_push_chunks: chunk_len must be positive")
+        n = len(syms)
+        return self._mset_push("ans_gpu_mset_push_chunks", lib().ans_gpu_mset_push_chunks, table, syms, (n, chunk_len),
+                               -(-n // chunk_len), chunk_len, data, offsets, lens)
+
+    def mset_pop_chunks(self, table, data, offsets, lens, n, chunk_len, dtype=np.uint32):
+        """MultisetShuffle::pop of chunk_len values from every message (n in all, the last chunk
+        the rest): returns (values in pop order, container of what remains)."""
+        if chunk_len <= 0:
+            raise AnsError(ANS_E_ARG, "mset_pop_chunks: chunk_len must be positive")
+        return self._mset_pop("ans_gpu_mset_pop_chunks", lib().ans_gpu_mset_pop_chunks, table, n, (n, chunk_len),
+                              -(-n // chunk_len), data, offsets, lens, dtype)
+
+    def mset_push_var_chunks(self, table, syms, starts, data, offsets, lens):
+        """mset_push_chunks over variable chunks: chunk c = positions [starts[c], starts[c+1])."""
+        where = "ans_gpu_mset_push_var_chunks"
+        st = self._resume_starts(where, starts, len(syms))
+        nchunks = len(st) - 1
+        longest = int(np.max(np.diff(st))) if nchunks else 0
+        return self._mset_push(where, lib().ans_gpu_mset_push_var_chunks, table, syms, (nchunks, _np_ptr(st)), nchunks,
+                               longest, data, offsets, lens)
+
+    def mset_pop_var_chunks(self, table, data, offsets, lens, starts, dtype=np.uint32):
+        where = "ans_gpu_mset_pop_var_chunks"
+        st = np.ascontiguousarray(np.asarray(starts, dtype=np.uint64))
+        n = int(st[-1]) if st.ndim == 1 and len(st) else 0
+        st = self._resume_starts(where, st, n)
+        nchunks = len(st) - 1
+        return self._mset_pop(where, lib().ans_gpu_mset_pop_var_chunks, table, n, (nchunks, _np_ptr(st)), nchunks, data,
+                              offsets, lens, dtype)
+
+    def dev_mset_push(self, table, d_syms, sym_bytes, n, chunk_len, d_slots, slot_cap, d_lens, d_status, stream=None,
+                      d_starts=None, nchunks=None):
+        """In place on device slots: d_lens is read and rewritten.  d_starts (nchunks + 1 u64 on the
+        device): variable chunks, n and chunk_len unused."""
+        if d_starts is not None:
+            _check(lib().ans_dev_mset_push_var(self.h, table, _dptr(d_syms), sym_bytes, nchunks, _dptr(d_starts),
+                                               _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+                   "ans_dev_mset_push_var")
+            return
+        _check(lib().ans_dev_mset_push(self.h, table, _dptr(d_syms), sym_bytes, n, chunk_len, _dptr(d_slots), slot_cap,
+                                       _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_mset_push")
+
+    def dev_mset_pop(self, table, d_slots, slot_cap, d_lens, n, chunk_len, d_syms, sym_bytes, d_status, stream=None,
+                     d_starts=None, nchunks=None):
+        if d_starts is not None:
+            _check(lib().ans_dev_mset_pop_var(self.h, table, _dptr(d_slots), slot_cap, _dptr(d_lens), nchunks,
+                                              _dptr(d_starts), _dptr(d_syms), sym_bytes, _dptr(d_status), _sptr(stream)),
+                   "ans_dev_mset_pop_var")
+            return
+        _check(lib().ans_dev_mset_pop(self.h, table, _dptr(d_slots), slot_cap, _dptr(d_lens), n, chunk_len,
+                                      _dptr(d_syms), sym_bytes, _dptr(d_status), _sptr(stream)), "ans_dev_mset_pop")
 
     def fast(self):
         """1 / 2: the set runs on the fast kernels (2: with voted exact renorm rows); 0: exact only."""

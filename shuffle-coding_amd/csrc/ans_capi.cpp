@@ -8,6 +8,7 @@
 // for it.
 #include <new>
 
+#include "ans_mset.hpp"
 #include "ans_table.hpp"
 
 using namespace shuffle_coding;
@@ -222,6 +223,76 @@ int ans_pop_iid(ans_msg* m, const ans_table* t, uint32_t* out, size_t n) {
     if (!m || !t || (n && !out)) return ANS_E_ARG;
     return guarded([&] {
         for (size_t k = 0; k < n; ++k) out[k] = static_cast<uint32_t>(t->cat.pop(m->m));  // src/codec.rs:423
+    });
+}
+
+// ---- recursive multiset shuffle coding on one message (ans_mset.hpp): ShuffleCodec<
+// IIDVecSliceCodecs<Categorical>, VecOrbitCodecs>, src/recursive/mod.rs:117-148
+uint64_t ans_orbit_id(uint64_t x) { return mset::orbit_id(x); }
+
+namespace {
+struct VecAcc {  // the counts' nodes in a vector
+    uint32_t* p;
+    uint32_t load(uint32_t i) const { return p[i]; }
+    void store(uint32_t i, uint32_t v) { p[i] = v; }
+};
+// the table's rank tables (built once per table; ANS_E_ARG for an alphabet the codec does not take)
+void need_ranks(const ans_table* t) {
+    const size_t nsym = t->cat.masses.size();
+    if (nsym == 0 || nsym > mset::kMaxSymbols) throw AnsError(ANS_E_ARG, "multiset alphabet outside 1..65536 symbols");
+    std::call_once(t->ranks_once,
+                   [&] { t->ranks_ok = mset::build_ranks(static_cast<uint32_t>(nsym), t->rank, t->sym_of_rank); });
+    if (!t->ranks_ok) throw AnsError(ANS_E_ARG, "two symbols share an orbit id");
+}
+}  // namespace
+
+int ans_mset_push(ans_msg* m, const ans_table* t, const uint32_t* syms, size_t n) {
+    if (!m || !t || (n && !syms)) return ANS_E_ARG;
+    return guarded([&] {
+        need_ranks(t);
+        if (n > 0xFFFFFFFFull) throw AnsError(ANS_E_ARG, "multiset of 2^32 or more values");
+        const Categorical& cat = t->cat;
+        const uint32_t nsym = static_cast<uint32_t>(cat.masses.size());
+        std::vector<uint32_t> nodes(nsym, 0);
+        mset::Counts<VecAcc> cnt{VecAcc{nodes.data()}, nsym};
+        for (size_t k = 0; k < n; ++k) {
+            if (cat.pmf(syms[k]) == 0) throw AnsError(ANS_E_ZERO_MASS, "assertion failed: pmf(x) != 0");
+            cnt.tally(t->rank[syms[k]]);
+        }
+        cnt.build();
+        Message& msg = m->m;
+        for (uint64_t L = n; L > 0; --L) {
+            // pop a rank under the orbit distribution of the L values left (src/ans.rs:107-116)
+            msg.renorm(L * (MAX_MIN_HEAD / L));
+            const uint64_t q = msg.head / L, cf = msg.head % L;
+            const mset::Found f = cnt.find(cf);
+            msg.head = f.count * q + (cf - f.cum);
+            cnt.add(f.rank, -1);
+            cat.push(msg, static_cast<uint64_t>(t->sym_of_rank[f.rank]));  // ... and push its symbol
+        }
+    });
+}
+
+int ans_mset_pop(ans_msg* m, const ans_table* t, uint32_t* out, size_t n) {
+    if (!m || !t || (n && !out)) return ANS_E_ARG;
+    return guarded([&] {
+        need_ranks(t);
+        if (n > 0xFFFFFFFFull) throw AnsError(ANS_E_ARG, "multiset of 2^32 or more values");
+        const Categorical& cat = t->cat;
+        const uint32_t nsym = static_cast<uint32_t>(cat.masses.size());
+        std::vector<uint32_t> nodes(nsym, 0);
+        mset::Counts<VecAcc> cnt{VecAcc{nodes.data()}, nsym};
+        Message& msg = m->m;
+        for (uint64_t k = 0; k < n; ++k) {
+            const uint64_t s = cat.pop(msg);
+            out[k] = static_cast<uint32_t>(s);
+            const uint32_t r = t->rank[s];
+            cnt.add(r, 1);
+            // push the rank under the orbit distribution of the k + 1 values so far (src/ans.rs:96-105)
+            const uint64_t p = cnt.count(r), c = cnt.prefix(r), norm = k + 1;
+            msg.renorm(p * (MAX_MIN_HEAD / norm));
+            msg.head = norm * (msg.head / p) + c + msg.head % p;
+        }
     });
 }
 

@@ -25,173 +25,20 @@
 #include <vector>
 
 #include "ans_ctx.hpp"
+#include "ans_exact.hpp"
 #include "ans_hostio.hpp"
 #include "ans_mfast_launch.hpp"
+
+// the lane's stream I/O (Sink, Source, RSource), the blanket push / pop (PushT, PopT), the table
+// set's model (TabHdr, CatSetModel), flatten and raise: ans_exact.hpp, shared with ans_mset.hip
+using namespace shuffle_coding::exact;
 
 namespace {
 
 using shuffle_coding::fast::ChunkInit;
-constexpr uint64_t kMaxMinHead = 1ull << 56;  // src/ans.rs:19
 constexpr uint64_t kMaxSize = 1ull << 46;     // src/ans.rs:22
-// one wave per workgroup: a chunk is one lane, and the few thousand chunks of a call spread over
-// every CU instead of filling a quarter of them with 256-lane workgroups
-constexpr int kThreads = 64;
-constexpr uint32_t kCatLdsMax = 48 * 1024;  // a table set at most this big is staged in LDS
 
 #define HIP_TRY(expr) ANS_HIP_TRY(expr)
-
-__device__ __forceinline__ void raise(uint32_t* status, int code) { atomicOr(status, 1u << code); }
-
-// ---- lane stream I/O
-// Encoder: bytes in push order into the lane's slot, 8 at a time, from position len on (0: a new
-// message; a resumed one, ans_dev_independent_push, has its len bytes already in the slot);
-// pop() takes back the last byte (a renorm_up during a push, src/ans.rs:239-243), or reports the
-// tail empty.  The slot may sit at any alignment (slot_cap is the caller's), so the 8-byte
-// accesses go through memcpy.
-struct Sink {
-    uint8_t* out;
-    uint64_t cap, pos, acc;
-    uint32_t nacc;
-    bool overflow;
-    __device__ Sink(uint8_t* slot, uint64_t slot_cap, uint64_t len)
-        : out(slot), cap(slot_cap), pos(len & ~uint64_t(7)), acc(0), nacc(static_cast<uint32_t>(len & 7)), overflow(false) {
-        for (uint32_t k = 0; k < nacc; ++k) acc |= static_cast<uint64_t>(out[pos + k]) << (8 * k);
-    }
-    __device__ void put(uint32_t byte) {
-        acc |= static_cast<uint64_t>(byte & 0xFFu) << (8 * nacc);
-        if (++nacc == 8) {
-            if (pos + 8 <= cap) __builtin_memcpy(out + pos, &acc, 8);
-            else overflow = true;
-            pos += 8;
-            acc = 0;
-            nacc = 0;
-        }
-    }
-    __device__ bool pop(uint32_t& byte) {
-        if (nacc == 0) {
-            if (pos == 0) return false;
-            pos -= 8;
-            acc = 0;
-            if (pos + 8 <= cap) __builtin_memcpy(&acc, out + pos, 8);
-            nacc = 8;
-        }
-        --nacc;
-        byte = static_cast<uint32_t>(acc >> (8 * nacc)) & 0xFFu;
-        acc &= nacc ? (~0ull >> (64 - 8 * nacc)) : 0ull;
-        return true;
-    }
-    __device__ uint64_t finish() {
-        if (pos + nacc > cap) overflow = true;
-        else
-            for (uint32_t k = 0; k < nacc; ++k) out[pos + k] = static_cast<uint8_t>(acc >> (8 * k));
-        return pos + nacc;
-    }
-};
-
-// Decoder: pops from the end of the stream (Tail::pop, src/ans.rs:198-203); past the start the
-// generator: Zeros gives 0, Empty is exhaustion (src/ans.rs:140-145), and any generated byte
-// means the message does not end where it began (a container stream holds no generated byte).
-// unpop() is renorm_down pushing a byte back (src/ans.rs:246-253).
-struct Source {
-    static constexpr bool kResume = false;
-    const uint8_t* in;
-    uint64_t len, pos;
-    uint32_t generated;
-    bool bad;
-    __device__ uint32_t pop() {
-        if (pos) return in[--pos];
-        ++generated;
-        return 0;
-    }
-    __device__ void unpop(uint32_t byte) {
-        if (generated) {
-            --generated;
-            bad |= byte != 0;
-        } else if (pos < len && in[pos] == byte) {
-            ++pos;
-        } else {
-            bad = true;
-        }
-    }
-};
-
-// Decoder of a resumed message (ans_dev_independent_pop: Message::unflatten(slot bytes) with the
-// Empty generator, src/ans.rs:262-264): pull() takes the byte below pos (false at the stream's
-// start: exhaustion); unpop() STORES the byte renorm_down hands back (src/ans.rs:246-253) at pos:
-// in a resumed message that byte is new data (the head's, which unflatten never saw as a stream
-// byte), not one to compare.
-struct RSource {
-    static constexpr bool kResume = true;
-    uint8_t* buf;
-    uint64_t cap, pos;
-    bool overflow, exhausted;
-    __device__ bool pull(uint64_t& head) {
-        if (!pos) {
-            exhausted = true;
-            return false;
-        }
-        head = (head << 8) | buf[--pos];
-        return true;
-    }
-    __device__ void unpop(uint32_t byte) {
-        if (pos < cap) buf[pos] = static_cast<uint8_t>(byte);
-        else overflow = true;
-        ++pos;
-    }
-};
-
-// ---- the blanket push / pop (src/ans.rs:96-116) for cdf(x, i) = c + i (Uniform, Categorical)
-// kRes: a resumed message, whose Empty tail ends the push at the first pull past the stream's
-// start (src/ans.rs:144)
-template <bool kRes>
-struct PushT {
-    static constexpr bool kResume = kRes;
-    uint64_t head;
-    Sink* sink;
-    uint32_t pulled;  // bytes a renorm_up had to draw from the generator (not in any stream)
-    // renorm(p * K) then head = norm*(head/p) + c + head%p; p = 1 needs no division
-    __device__ void push(uint64_t p, uint64_t norm, uint64_t K, uint64_t c) {
-        const uint64_t bound = p * K;
-        while (head < bound) {  // renorm_up: take back the last pushed byte
-            uint32_t b = 0;
-            if (!sink->pop(b)) {
-                ++pulled;
-                if constexpr (kResume) return;
-            }
-            head = (head << 8) | b;
-        }
-        while ((head >> 8) >= bound) {  // renorm_down
-            sink->put(static_cast<uint32_t>(head));
-            head >>= 8;
-        }
-        if (p == 1) head = norm * head + c;
-        else head = norm * (head / p) + c + head % p;
-    }
-};
-using Push = PushT<false>;
-// Src: Source, or the resumed message's RSource below (any number of zero bytes may lie on top of
-// it: the pull runs until the bound is met or the stream ends)
-template <class Src>
-struct PopT {
-    uint64_t head;
-    Src* src;
-    // renorm(norm * K), then (q, cf) = head divmod norm
-    __device__ void renorm(uint64_t norm, uint64_t K) {
-        const uint64_t bound = norm * K;
-        if constexpr (Src::kResume) {
-            while (head < bound && src->pull(head)) {}
-            if (head < bound) return;
-        } else {
-            for (int g = 0; head < bound && g < 9; ++g) head = (head << 8) | src->pop();
-            if (head < bound) src->bad = true;  // only zero bytes past the start: corrupt
-        }
-        while ((head >> 8) >= bound) {
-            src->unpop(static_cast<uint32_t>(head) & 0xFFu);
-            head >>= 8;
-        }
-    }
-};
-using Pop = PopT<Source>;
 
 // ---- the models
 // Each model splits an element into what can be loaded ahead of the chain (Elem: the symbol and,
@@ -253,87 +100,10 @@ struct LogUniformModel {  // IID<LogUniform(E)>: bits = 64 - clz(x) by Uniform(E
     }
 };
 
-// A set of Categoricals with u64 cdf values (norm up to 2^56): table t's cdf at cum + hdr.cum_off
-// (nsym + 1 entries, the last = norm), its icdf buckets at bkt + hdr.bkt_off (nb + 1 entries).
-// When the whole set fits (lds_bytes > 0) each workgroup stages it in LDS first: the image is
-// cum | bkt | hdr at the same offsets as in global memory, one contiguous block.
-struct TabHdr {
-    uint64_t cum_off, bkt_off, norm, K;
-    uint32_t nsym, shift;
-};
-struct CatSetModel {
-    const uint64_t* cum;
-    const uint32_t* bkt;
-    const TabHdr* hdr;
-    const uint32_t* tid;  // table of each position (NULL: table 0 everywhere, or tid8)
-    const uint8_t* tid8;  // ... as one byte per position (sets of at most 256 tables)
-    uint32_t ntables;
-    uint32_t lds_bytes;   // the set's image size when it is staged in LDS, else 0
-    struct Elem { uint64_t x; uint32_t t; };
-    struct Pos { uint32_t t; };
-    // stage the image into LDS (every thread of the workgroup, before any returns)
-    __device__ void stage(unsigned char* lds) {
-        if (!lds_bytes) return;
-        const uint4* g = reinterpret_cast<const uint4*>(cum);
-        uint4* d = reinterpret_cast<uint4*>(lds);
-        for (uint32_t i = threadIdx.x; i < lds_bytes / 16; i += blockDim.x) d[i] = g[i];
-        __syncthreads();
-        const char* gb = reinterpret_cast<const char*>(cum);
-        bkt = reinterpret_cast<const uint32_t*>(lds + (reinterpret_cast<const char*>(bkt) - gb));
-        hdr = reinterpret_cast<const TabHdr*>(lds + (reinterpret_cast<const char*>(hdr) - gb));
-        cum = reinterpret_cast<const uint64_t*>(lds);
-    }
-    __device__ uint32_t table_of(uint64_t k) const { return tid ? tid[k] : tid8 ? tid8[k] : 0u; }
-    template <typename Sym>
-    __device__ Elem load(const Sym* syms, uint64_t k) const {
-        return Elem{static_cast<uint64_t>(syms[k]), table_of(k)};
-    }
-    __device__ Pos pos(uint64_t k) const { return Pos{table_of(k)}; }
-    template <class P>
-    __device__ int push(P& m, const Elem& e) const {
-        const TabHdr h = hdr[e.t];
-        if (e.x >= h.nsym) return ANS_E_SYMBOL;  // src/codec.rs:63
-        const uint64_t* c = cum + h.cum_off;
-        const uint64_t lo = c[e.x], p = c[e.x + 1] - lo;
-        if (p == 0) return ANS_E_ZERO_MASS;  // src/ans.rs:98
-        m.push(p, h.norm, h.K, lo);
-        return ANS_OK;
-    }
-    template <class P>
-    __device__ uint64_t pop(P& m, const Pos& ps) const {
-        const TabHdr h = hdr[ps.t];
-        m.renorm(h.norm, h.K);
-        const uint64_t q = m.head / h.norm, cf = m.head - q * h.norm;
-        const uint64_t* c = cum + h.cum_off;
-        // icdf (src/codec.rs:65-68): the last x with cdf(x) <= cf, between the bucket's first
-        // symbol icdf(j << shift) and the next bucket's (bkt holds nb + 1 entries per table), by
-        // binary search: at most log2 of the bucket's symbol count reads
-        const uint64_t j = h.bkt_off + (cf >> h.shift);
-        uint64_t lo = bkt[j], hi = bkt[j + 1];
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (c[mid] <= cf) lo = mid;
-            else hi = mid - 1;
-        }
-        m.head = (c[lo + 1] - c[lo]) * q + (cf - c[lo]);
-        return lo;
-    }
-};
-
 // ---- the kernels' shared steps
 // Elements are loaded kPrefetch at a time, one block ahead of the block being coded (the loads
 // of a block are independent of the chain: their HBM latency overlaps kPrefetch steps).
 constexpr int kPrefetch = 8;
-
-// flatten (src/ans.rs:255-260): renorm_down(1), then the last head byte
-template <class Put>
-__device__ __forceinline__ void flatten(uint64_t head, Put put) {
-    while ((head >> 8) >= 1) {
-        put(static_cast<uint32_t>(head));
-        head >>= 8;
-    }
-    put(static_cast<uint32_t>(head));
-}
 
 // The end of a decode, assert_eq!(initial, m) (src/ans.rs:56): the head pulled back up to the
 // initial message's (chunk c's, worked out only once everything else holds), no byte left.  A pop
@@ -970,6 +740,7 @@ struct ans_gpu_tableset {
     double max_bits;  // largest log2(norm / pmin) over the tables: sizes the slots
     IndepFast fast;   // ans_mfast.hpp images when every table is in the fast range
     std::vector<uint32_t> nsym;  // symbols per table (host copy: argument checks)
+    MsetState* mset = nullptr;   // rank tables of the multiset calls (ans_mset.hip), built on first use
 };
 
 namespace {
@@ -1268,8 +1039,12 @@ void ans_tableset_destroy(ans_gpu_tableset* ts) {
     (void)hipSetDevice(ts->device);
     (void)hipFree(ts->d_mem);
     if (ts->fast.d_mem) (void)hipFree(ts->fast.d_mem);
+    ans_mset_state_free(ts->mset);
     delete ts;
 }
+const CatSetModel& ans_tableset_model(const ans_gpu_tableset* ts) { return ts->md; }
+const std::vector<uint32_t>& ans_tableset_nsyms(const ans_gpu_tableset* ts) { return ts->nsym; }
+MsetState*& ans_tableset_mset(ans_gpu_tableset* ts) { return ts->mset; }
 
 // ---- staging: host buffers in and out
 namespace {

@@ -29,6 +29,8 @@ struct ans_gpu {
     void* d_scratch;       // device scratch of the device-resident graph calls (ans_graph.hip)
     size_t cap_scratch;
     LaunchLog last;  // the last launcher call's coder kernels (ans_gpu_last_launch)
+    void* d_mset_ws = nullptr;  // per-lane counts of the multiset kernels' global form (ans_mset.hip)
+    size_t cap_mset_ws = 0;
 };
 
 struct ans_gpu_table {

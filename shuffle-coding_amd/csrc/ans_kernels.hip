@@ -703,6 +703,8 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
         case kRecDecode64: w = std::snprintf(o, room - 1, "k_decode64<catset,%s>", sym); break;
         case kRecPush64: w = std::snprintf(o, room - 1, "k_push64<%s>", sym); break;
         case kRecPop64: w = std::snprintf(o, room - 1, "k_pop64<%s>", sym); break;
+        case kRecMsetPush: w = std::snprintf(o, room - 1, "k_mset_push<%s,cnt=%s>", sym, a[0] ? "lds" : "global"); break;
+        case kRecMsetPop: w = std::snprintf(o, room - 1, "k_mset_pop<%s,cnt=%s>", sym, a[0] ? "lds" : "global"); break;
         default: w = std::snprintf(o, room - 1, "?"); break;
         }
         at += static_cast<size_t>(w);
@@ -720,6 +722,7 @@ void ans_gpu_free(ans_gpu* g) try {
     (void)hipSetDevice(g->device);
     ans_pipe_free(g);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
+    if (g->d_mset_ws) (void)hipFree(g->d_mset_ws);
     (void)hipStreamDestroy(g->stream);
     delete g;
 } ANS_CATCH_VOID

@@ -24,6 +24,8 @@ enum LaunchKind : uint8_t {
     kRecDecode64,
     kRecPush64,
     kRecPop64,
+    kRecMsetPush,       // k_mset_push / k_mset_pop (ans_mset.hip)  a = {counts in LDS (1) or global memory (0)}
+    kRecMsetPop,
 };
 struct LaunchRec {
     uint8_t kind;

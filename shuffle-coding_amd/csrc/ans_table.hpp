@@ -3,6 +3,8 @@
 #pragma once
 
 #include <cstdint>
+#include <mutex>
+#include <vector>
 
 #include "ans_core.hpp"
 
@@ -13,6 +15,12 @@ struct ans_msg {
 
 struct ans_table {
     shuffle_coding::Categorical cat;  // Categorical::new(masses)  src/codec.rs:72-80
+    explicit ans_table(shuffle_coding::Categorical c) : cat(std::move(c)) {}
+    // the alphabet's rank tables (ans_mset.hpp build_ranks), built by the first multiset call on
+    // this table (ans_capi.cpp: under ranks_once, a table may be shared between threads)
+    mutable std::once_flag ranks_once;
+    mutable std::vector<uint32_t> rank, sym_of_rank;
+    mutable bool ranks_ok = false;
 };
 
 namespace shuffle_coding {

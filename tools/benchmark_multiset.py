@@ -1,5 +1,5 @@
 """Config C1: the reference's `cargo test --release benchmark_multiset -- --ignored`
-(src/multiset.rs:155-175), vector part, on this library.
+(src/multiset.rs:155-184) on this library.
 
 For each fixture multiset-data/{1000,10000,100000}.txt (tests/golden/): the IID<Categorical>
 with the reference's table (masses max(1, floor(p * 2^28)), src/multiset.rs:169-170) is run
@@ -7,7 +7,9 @@ through Codec::test with TestConfig::test(0)'s initial message Message::random(0
 (src/benchmark.rs:590-595,698-700), printing `bits amortized_bits enc_sec dec_sec` like
 test_and_print.  Host coder (ans_core.hpp through the C ABI) first; with a GPU, the C2 layout
 too (64 chunks = one wave of chains, Message::zeros() per chunk, device-resident timing).
-The "as multiset with shuffle coding" half of the harness is out of scope.
+Then the harness's "...as multiset with shuffle coding" lines (src/multiset.rs:176-181): the same
+vector through iid_multiset_shuffle_codec, three timed runs, on the host path
+(ans_amd.MultisetShuffle over ans_mset_push / ans_mset_pop).
 """
 import json
 import os
@@ -71,9 +73,19 @@ def main():
                              "enc_sec": float(np.median(te)), "dec_sec": float(np.median(td))}
             print(f"  GPU, {nch} chunks of {L}: {row['gpu_c2']['bytes']} bytes, "
                   f"enc {row['gpu_c2']['enc_sec']:.3e} s, dec {row['gpu_c2']['dec_sec']:.3e} s")
+        # the harness's second half (src/multiset.rs:176-181): the same vector as a multiset, three runs
+        print()
+        print("...as multiset with shuffle coding:")
+        row["multiset"] = []
+        for _ in range(3):
+            res = A.MultisetShuffle(cat, size).test(v, A.Message.random(0))
+            print(f"{res.bits} {res.amortized_bits} {res.enc_sec} {res.dec_sec} ")
+            print()
+            row["multiset"].append({"bits": res.bits, "amortized_bits": res.amortized_bits, "enc_sec": res.enc_sec,
+                                    "dec_sec": res.dec_sec})
         rows.append(row)
         print()
-    print(json.dumps({"config": "C1 benchmark_multiset (vector part)", "rows": rows}))
+    print(json.dumps({"config": "C1 benchmark_multiset (vector and multiset parts)", "rows": rows}))
 
 
 if __name__ == "__main__":
