@@ -22,9 +22,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 #include <utility>
 
 #include "ans_dec_u.hpp"
+#include "ans_funnel.hpp"
 #include "ans_renorm.hpp"
 #include "ans_table.hpp"
 
@@ -313,10 +315,20 @@ __device__ __forceinline__ void put_sym(uint4& v, int j, uint32_t s) {
 // and stores only dword w (one ds_write_b32).  Dword w+1, when the push reached it, becomes X:
 // the next push (or finish) stores it with its own bytes, before any page holding it completes.
 // Bytes past the new end are garbage that the next push overwrites.
+// Nine VALU per push, any k up to four bytes: the funnel of k_encode's KMAX = 4 instantiations
+// and of ans_wide.hpp (ans_mfast.hpp has its own copy).  The instantiations whose pushes stay at
+// three bytes or fewer take the sliding window of ans_funnel.hpp, six VALU (EncFunnel below).
 template <uint32_t kBase>
 struct FunnelT {
     uint32_t X, pos8, neg8, addr, col;  // addr = ring address of dword pos/4 (row | col)
 
+    __device__ __forceinline__ static FunnelT start(uint32_t col) { return FunnelT{0, 0, 0, col, col}; }
+    __device__ __forceinline__ uint32_t end8() const { return pos8; }
+    // the low nb = 7 or 8 bytes of a head (the flatten, src/ans.rs:255-260)
+    __device__ __forceinline__ void push_head(uint64_t head, uint32_t nb) {
+        push(lo32(head), 32);
+        push(hi32(head), 8 * (nb - 4));
+    }
     __device__ __forceinline__ void push(uint32_t lo, uint32_t k8) {
         uint32_t xv, d0, d1;
         asm("v_bfe_u32 %0, %1, 0, %2" : "=v"(xv) : "v"(X), "v"(pos8));
@@ -337,7 +349,16 @@ struct FunnelT {
         *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr + kBase)) = xv;
     }
 };
-using Funnel = FunnelT<kEncRingBase>;
+// the window funnel's ring store: one aligned ds_write_b32 at kBase + addr
+template <uint32_t kBase>
+struct LdsStoreT {
+    __device__ __forceinline__ static void st(uint32_t addr, uint32_t v) {
+        *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr + kBase)) = v;
+    }
+};
+// k_encode's funnel by KMAX: the sliding window while no push exceeds three bytes
+template <int KMAX>
+using EncFunnel = std::conditional_t<(KMAX <= 3), WindowFunnelT<LdsStoreT<kEncRingBase>>, FunnelT<kEncRingBase>>;
 
 // Completed ring pages leave in aligned pairs, one whole 128-B line per lane: the even page
 // waits in registers for its odd partner.  A lone 64-B store leaves its line half-written in L2
@@ -466,13 +487,13 @@ __global__ __launch_bounds__(kBlock, kGlobalRows ? 2 : 4) void k_encode(FastTabl
     const uint32_t exp_norm = 0x43300000u * static_cast<uint32_t>(t.norm);  // the estimate's exponent word x norm
 
     uint64_t head = ini.head(c);  // Message::zeros() / random(seed + c)
-    Funnel f{0, 0, 0, ring.col, ring.col};
+    auto f = EncFunnel<KMAX>::start(ring.col);
     uint32_t fp = 0, over = 0;
     uint32_t minmass = ~0u;  // 0 after a zero-mass / out-of-range symbol (push_one's voted branch)
 
     auto point = [&]() __attribute__((always_inline)) {
         wait_vm();
-        if ((f.pos8 >> 9) > fp) {  // at most one page completes per unit (U * KMAX <= 64 bytes)
+        if ((f.end8() >> 9) > fp) {  // at most one page completes per unit (U * KMAX <= 64 bytes)
             if (fp < npages_cap) pout.page(ring, fp, dst);
             else over = 1;
             ++fp;
@@ -647,7 +668,7 @@ __global__ __launch_bounds__(kBlock, kGlobalRows ? 2 : 4) void k_encode(FastTabl
             for (int i = 0; i < GU; ++i) n[i] = load_sym(gsrc + i);
         }
         auto flush_ready = [&]() __attribute__((always_inline)) {
-            if ((f.pos8 >> 9) > fp) {
+            if ((f.end8() >> 9) > fp) {
                 if (fp < npages_cap) pout.page(ring, fp, dst);
                 else over = 1;
                 ++fp;
@@ -682,8 +703,7 @@ __global__ __launch_bounds__(kBlock, kGlobalRows ? 2 : 4) void k_encode(FastTabl
     // flatten (src/ans.rs:255-260): all significant head bytes, low first (7 or 8 here,
     // since the head is >= norm*K > 2^55 after any push).
     const uint32_t nb = (71u - static_cast<uint32_t>(__builtin_clzll(head))) >> 3;
-    f.push(lo32(head), 32);
-    f.push(hi32(head), 8 * (nb - 4));
+    f.push_head(head, nb);
     f.finish();
     const uint32_t len = f.len();
     for (const uint32_t last = (len + 63) / 64; fp < last; ++fp) {
