@@ -28,6 +28,7 @@
 #include "ans_dec_u.hpp"
 #include "ans_funnel.hpp"
 #include "ans_renorm.hpp"
+#include "ans_ring.hpp"
 #include "ans_table.hpp"
 
 namespace shuffle_coding {
@@ -103,36 +104,6 @@ constexpr int kNormStd = 0;
 constexpr int kNormSmall = 1;
 constexpr int kNormBig = 2;
 
-// Non-temporal 16-byte global load / store (streamed data that must not evict cached tables).
-typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 nt_load(const uint4* p) {
-    const v4u32 v = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void nt_store(uint4* p, const uint4& v) {
-    __builtin_nontemporal_store(v4u32{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u32*>(p));
-}
-
-// s_waitcnt vmcnt(0) (gfx9 encoding; expcnt/lgkmcnt left at their maxima).
-__device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-// s_waitcnt vmcnt(N): all but the N youngest vector-memory operations done (in issue order)
-template <int N>
-__device__ __forceinline__ void wait_vm_n() {
-    static_assert(N >= 0 && N < 64, "vmcnt field");
-    __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
-}
-
-// x << S in 16 bits (the upper half of the result is zero on gfx950): v_lshlrev_b16 issues in
-// ~2.5 cycles per wave64 instruction where v_lshlrev_b32 and its SDWA forms take ~4.4
-// (tools/b16_probe.hip), so LDS addresses below 2^16 are formed with it
-template <int S>
-__device__ __forceinline__ uint32_t shl16(uint32_t x) {
-    static_assert(S >= 0 && S < 16, "16-bit shift");
-    uint32_t r;
-    asm("v_lshlrev_b16 %0, %1, %2" : "=v"(r) : "I"(S), "v"(x));
-    return r;
-}
-
 // f(integral_constant<int, I>) for each I in order, every call inlined: a loop unrolled by
 // construction, so register arrays indexed by I stay in registers
 template <typename F, int... I>
@@ -140,9 +111,6 @@ __device__ __forceinline__ void unroll_seq(F&& f, std::integer_sequence<int, I..
     (f(std::integral_constant<int, I>{}), ...);
 }
 
-__device__ __forceinline__ uint32_t ab(uint32_t hi, uint32_t lo, uint32_t s) {
-    return __builtin_amdgcn_alignbyte(hi, lo, s);
-}
 __device__ __forceinline__ uint32_t lo32(uint64_t x) { return static_cast<uint32_t>(x); }
 __device__ __forceinline__ uint32_t hi32(uint64_t x) { return static_cast<uint32_t>(x >> 32); }
 __device__ __forceinline__ uint64_t mk64(uint32_t hi, uint32_t lo) { return (static_cast<uint64_t>(hi) << 32) | lo; }
@@ -247,32 +215,11 @@ struct ChunkInit {
     }
 };
 
-// Lane-private ring of 32 dwords in a [dword][lane] image.
-// LDS accesses by byte offset (address space 3): keeps the address arithmetic in 32 bits
-// where the compiler otherwise adds the (zero) LDS base or splits constants out of offsets.
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(3))) uint64_t lds_u64;
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-__device__ __forceinline__ uint32_t lds_ld32(uint32_t off) { return *reinterpret_cast<const lds_u32*>(static_cast<uintptr_t>(off)); }
-__device__ __forceinline__ uint64_t lds_ld64(uint32_t off) { return *reinterpret_cast<const lds_u64*>(static_cast<uintptr_t>(off)); }
-typedef __attribute__((address_space(3))) v4u32 lds_v4u32;
-__device__ __forceinline__ uint4 lds_ld128(uint32_t off) {
-    const v4u32 v = *reinterpret_cast<const lds_v4u32*>(static_cast<uintptr_t>(off));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// at kBase (kEncRingBase for the LDS-row encoder): a row address is one v_and_or of the row bits
-// and the lane's column
+// The LDS-row encoder's ring (ans_ring.hpp): 512 lanes at kBase (kEncRingBase for k_encode; k_encode_w
+// puts it at WideEncLds::ring), addresses by v_lshlrev_b16
 template <uint32_t kBase>
-struct RingT {
-    uint32_t col;  // 4 * lane
-    __device__ __forceinline__ lds_u32& at(int32_t i) const {
-        const uint32_t a = ((static_cast<uint32_t>(i) << 11) & 0xF800u) | col;
-        return *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(a + kBase));
-    }
-};
-using Ring = RingT<kEncRingBase>;
+using EncLay = RingLayout<kBlock, kBase, 8, kRowShl16>;
+using Ring = RingT<EncLay<kEncRingBase>>;
 
 // 8 * byte b of w in one SDWA shift (an LDS row offset straight from a u8 symbol; for byte 0
 // the compiler emitted a shift and a mask).  b is a compile-time constant after unrolling.
@@ -306,49 +253,6 @@ __device__ __forceinline__ void put_sym(uint4& v, int j, uint32_t s) {
 }
 
 // ====================================================================== encode
-// Byte funnel.  pos8 = 8 * (stream bytes so far), neg8 = -pos8; the stream's dword w = pos/4
-// lives in ring row w & 31, and X holds its contents with the b = pos & 3 written bytes at the
-// bottom (garbage above).  A push of the head's low k bytes (lo, little-endian = stream order,
-// src/ans.rs:246-253) forms both dwords it can touch, whatever k is:
-//   dword w   = X's b bytes | lo << 8b           (v_bfe_u32 + v_lshl_or_b32)
-//   dword w+1 = lo >> (32 - 8b)                  (v_lshrrev_b32; for b = 0 all of lo: unused bytes)
-// and stores only dword w (one ds_write_b32).  Dword w+1, when the push reached it, becomes X:
-// the next push (or finish) stores it with its own bytes, before any page holding it completes.
-// Bytes past the new end are garbage that the next push overwrites.
-// Nine VALU per push, any k up to four bytes: the funnel of k_encode's KMAX = 4 instantiations
-// and of ans_wide.hpp (ans_mfast.hpp has its own copy).  The instantiations whose pushes stay at
-// three bytes or fewer take the sliding window of ans_funnel.hpp, six VALU (EncFunnel below).
-template <uint32_t kBase>
-struct FunnelT {
-    uint32_t X, pos8, neg8, addr, col;  // addr = ring address of dword pos/4 (row | col)
-
-    __device__ __forceinline__ static FunnelT start(uint32_t col) { return FunnelT{0, 0, 0, col, col}; }
-    __device__ __forceinline__ uint32_t end8() const { return pos8; }
-    // the low nb = 7 or 8 bytes of a head (the flatten, src/ans.rs:255-260)
-    __device__ __forceinline__ void push_head(uint64_t head, uint32_t nb) {
-        push(lo32(head), 32);
-        push(hi32(head), 8 * (nb - 4));
-    }
-    __device__ __forceinline__ void push(uint32_t lo, uint32_t k8) {
-        uint32_t xv, d0, d1;
-        asm("v_bfe_u32 %0, %1, 0, %2" : "=v"(xv) : "v"(X), "v"(pos8));
-        asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(d0) : "v"(lo), "v"(pos8), "v"(xv));
-        asm("v_lshrrev_b32 %0, %1, %2" : "=v"(d1) : "v"(neg8), "v"(lo));
-        *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr + kBase)) = d0;
-        pos8 += k8;
-        neg8 -= k8;
-        const uint32_t a = (shl16<6>(pos8) & 0xF800u) | col;  // (pos8 << 6) & 0xF800 needs 16 bits
-        X = a != addr ? d1 : d0;
-        addr = a;
-    }
-    __device__ __forceinline__ uint32_t len() const { return pos8 >> 3; }
-    // the partial last dword, zero-padded, into its ring row (nothing is pushed after this)
-    __device__ __forceinline__ void finish() {
-        uint32_t xv;
-        asm("v_bfe_u32 %0, %1, 0, %2" : "=v"(xv) : "v"(X), "v"(pos8));
-        *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr + kBase)) = xv;
-    }
-};
 // the window funnel's ring store: one aligned ds_write_b32 at kBase + addr
 template <uint32_t kBase>
 struct LdsStoreT {
@@ -358,52 +262,7 @@ struct LdsStoreT {
 };
 // k_encode's funnel by KMAX: the sliding window while no push exceeds three bytes
 template <int KMAX>
-using EncFunnel = std::conditional_t<(KMAX <= 3), WindowFunnelT<LdsStoreT<kEncRingBase>>, FunnelT<kEncRingBase>>;
-
-// Completed ring pages leave in aligned pairs, one whole 128-B line per lane: the even page
-// waits in registers for its odd partner.  A lone 64-B store leaves its line half-written in L2
-// until the next page, and the streaming traffic around it evicts such lines in pieces (1.2x
-// the stream's bytes written, profiles/r02c_pmc_c3_summary.txt; the 128-B symbol stores of
-// k_decode write exactly theirs, profiles/r02d_pmc_c3_summary.txt).
-template <uint32_t kBase>
-struct PageOut {
-    uint4 h0, h1, h2, h3;  // page 2m, until 2m+1 completes
-    __device__ __forceinline__ void page(const RingT<kBase>& ring, uint32_t p, uint8_t* dst) {
-        uint32_t w[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = ring.at(static_cast<int32_t>(16 * p + i));
-        const uint4 v0 = make_uint4(w[0], w[1], w[2], w[3]), v1 = make_uint4(w[4], w[5], w[6], w[7]);
-        const uint4 v2 = make_uint4(w[8], w[9], w[10], w[11]), v3 = make_uint4(w[12], w[13], w[14], w[15]);
-        if (p & 1) {
-            uint4* d = reinterpret_cast<uint4*>(dst + 64ull * (p - 1));
-            d[0] = h0;
-            d[1] = h1;
-            d[2] = h2;
-            d[3] = h3;
-            d[4] = v0;
-            d[5] = v1;
-            d[6] = v2;
-            d[7] = v3;
-        }
-        // held unconditionally (an odd page's copy is dead): as an else branch the compiler
-        // merged these writes with the stores above into stores through a selected pointer,
-        // which put the held page in scratch
-        h0 = v0;
-        h1 = v1;
-        h2 = v2;
-        h3 = v3;
-    }
-    // after the last page: np pages completed in all (an odd count leaves the last one held)
-    __device__ __forceinline__ void finish(uint32_t np, uint8_t* dst) {
-        if (np & 1) {
-            uint4* d = reinterpret_cast<uint4*>(dst + 64ull * (np - 1));
-            d[0] = h0;
-            d[1] = h1;
-            d[2] = h2;
-            d[3] = h3;
-        }
-    }
-};
+using EncFunnel = std::conditional_t<(KMAX <= 3), WindowFunnelT<LdsStoreT<kEncRingBase>>, FunnelT<EncLay<kEncRingBase>>>;
 
 // KMAX: most bytes one push can emit (table property); kK32: K < 2^32 (norm > 2^24).
 // kGlobalRows: the rows stay in global memory (alphabets above 256 symbols, e.g. C4's 65,536:
@@ -472,7 +331,7 @@ __global__ __launch_bounds__(kBlock, kGlobalRows ? 2 : 4) void k_encode(FastTabl
         return r;
     };
     const Ring ring{4 * threadIdx.x};
-    PageOut<kEncRingBase> pout;
+    PageOut pout;
     __syncthreads();
     const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (c >= nfull) return;
@@ -837,181 +696,37 @@ __device__ __forceinline__ void clear_below(uint4& a0, uint4& a1, uint4& a2, uin
 }
 
 // ====================================================================== decode
-// One decode chain = one chunk, read from the end.  P is the stream position minus 4: the
-// window W = stream bytes [P, P+4) (byte P+3 on top) comes from ring dwords y = P>>2 and y+1
-// with one v_alignbyte.  The ring (after the tables, at kDecTableBytes) is [row][lane] with kDecRows = 33 rows:
-// row 32 mirrors row 0, so y and y+1 are one ds_read2st64_b32 even across the wrap.  Pages
-// (16 rows) land at points: page low+1 is free once dword y+1 lies in page low, and the page
-// below `low` is always in flight in registers (S); pages below 0 are zeros (the Zeros
-// generator, src/ans.rs:160-170).  A point covers at most 60 stream bytes (SPP symbols of at
-// most KMAX bytes), so no read between points can reach an unlanded page.
+// k_decode's chain: the stream ring of ans_ring.hpp (DecRingT: pages, window, points) with positions
+// in bits, after the tables (at kDecTableBytes), plus the coding steps below.
 // The decoder runs 1,024-lane workgroups, one per CU: the lanes share ONE copy of the tables,
 // so the whole 160 KiB of LDS holds the 1,024 rings (132 KiB) plus 28 KiB of tables, twice the
 // table room two 512-lane workgroups would leave (finer icdf buckets: C3 resolves every cf with
 // three candidates and compiles no far path).
-__device__ const uint4 kZeroPage[8] = {};  // 128 zero bytes: the Zeros tail generator's pages
 constexpr int kDecBlock = 1024;
-constexpr int kDecRows = 33;
+constexpr int kDecRows = kDecRingRows;
 constexpr uint32_t kDecRingBytes = kDecRows * kDecBlock * 4;
 static_assert(kDecRingBytes + kDecTableBytes == 160 * 1024, "decode LDS = one CU's 160 KiB");
 // decode LDS: the tables at offset 0 (bucket = cf bucket * 16, its s0 byte at the bucket index
 // plus an immediate offset), the ring after them at kDecTableBytes (a multiple of 256 B, folded
 // into the window read's ds_read2st64 offsets)
 static_assert(kDecTableBytes % 256 == 0 && kDecTableBytes / 256 + 16 <= 255, "ring base in the st64 offsets");
+// (the mirror row through the generic pointer ch.ring, as this kernel always wrote it: written
+// from col, as the other two chains do, k_decode comes out four instructions shorter and its
+// staged u16 forms spill one or two VGPRs fewer: a change of code, left for a round that measures it)
+using DecLay = RingLayout<kDecBlock, kDecTableBytes, 8, kRowLshlOr7, false, true>;
 
-struct DecChain {
-    uint32_t* ring;  // &ring[0][lane]
-    const uint8_t* src;
-    uint4 Q[8];  // the aligned page pair (2m, 2m+1) not yet landed: one 128-B L2 line per fetch
-    int32_t low, P8, sh;  // P8 = 8 P (P: the window's stream position); sh = 0 (stream-relative)
-    uint32_t W;
-    uint64_t head;
+struct DecChain : DecRingT<DecLay> {
     // per-step values between the phases
     uint64_t qq;
     uint32_t cf, cum, nxt, sx;
     bool far;
 
-    __device__ __forceinline__ uint32_t& row(int32_t r) const { return ring[r * kDecBlock]; }
-    // page p (its half of Q) into ring slot p & 1
-    // (positions count from the stream's start, so no landed page holds another stream's
-    // bytes: pages below the start are the zero page; nothing to clear)
-    // The sixteen rows go out as eight ds_write2st64_b32 from one base address (ring row r0):
-    // rows 4 KiB apart are 16 st64 units, so rows r0..r0+15 fit the 8-bit offset fields.  As C++
-    // stores the compiler formed each row's address with its own v_add (the rows lie beyond
-    // the 16-bit byte offsets) and stored them one dword at a time.
-    template <int R0>
-    __device__ __forceinline__ uint32_t put_half(uint4 a0, uint4 a1, uint4 a2, uint4 a3) {
-        const uint32_t base = col + kDecTableBytes + R0 * kDecBlock * 4;
-        asm volatile(
-            "ds_write2st64_b32 %0, %1, %2 offset0:0 offset1:16\n\t"
-            "ds_write2st64_b32 %0, %3, %4 offset0:32 offset1:48\n\t"
-            "ds_write2st64_b32 %0, %5, %6 offset0:64 offset1:80\n\t"
-            "ds_write2st64_b32 %0, %7, %8 offset0:96 offset1:112\n\t"
-            "ds_write2st64_b32 %0, %9, %10 offset0:128 offset1:144\n\t"
-            "ds_write2st64_b32 %0, %11, %12 offset0:160 offset1:176\n\t"
-            "ds_write2st64_b32 %0, %13, %14 offset0:192 offset1:208\n\t"
-            "ds_write2st64_b32 %0, %15, %16 offset0:224 offset1:240"
-            :
-            : "v"(base), "v"(a0.x), "v"(a0.y), "v"(a0.z), "v"(a0.w), "v"(a1.x), "v"(a1.y), "v"(a1.z), "v"(a1.w),
-              "v"(a2.x), "v"(a2.y), "v"(a2.z), "v"(a2.w), "v"(a3.x), "v"(a3.y), "v"(a3.z), "v"(a3.w)
-            : "memory");
-        return a0.x;
-    }
-    // two exec-masked store sets, one per parity: as one store set from selected registers the
-    // compiler spent 16 v_cndmask per landing (the barrier keeps it from merging them again)
-    __device__ __forceinline__ void put_page(int32_t p) {
-        if (p & 1) {
-            put_half<16>(Q[4], Q[5], Q[6], Q[7]);
-        } else {
-            row(32) = put_half<0>(Q[0], Q[1], Q[2], Q[3]);  // row 32 mirrors row 0
-        }
-    }
-    // pages are fetched as aligned 128-B pairs (2m, 2m+1): a 64-B read leaves the other half of
-    // its 128-B line to be fetched again later (profiles/r02_hbm_calib.txt: 2x the bytes).
-    // Pairs below 0 come from a zero pair in global memory: the same loads, where a register
-    // zero-fill cost a point's worth of v_mov on every wave with one lane at its stream start
-    // (global address space: a flat load would also count in lgkmcnt and stall the LDS waits)
-    // Positions count from the stream's first byte (src), at any alignment: a pair below the
-    // top one lies wholly inside the stream, so its 16-B loads (unaligned in a dense container;
-    // the hardware runs in unaligned mode) touch only the stream's own bytes.
-    __device__ __forceinline__ void fetch_pair(int32_t m) {
-        typedef __attribute__((address_space(1), aligned(1))) const v4u32 gv4;
-        const uint4* g = m >= 0 ? reinterpret_cast<const uint4*>(src + 128ll * m) : kZeroPage;
-        const gv4* gg = reinterpret_cast<const gv4*>(reinterpret_cast<uintptr_t>(g));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const v4u32 v = gg[k];
-            Q[k] = make_uint4(v.x, v.y, v.z, v.w);
-        }
-    }
-    // the top pair m (once per stream) may reach past the stream's end, where a wide load could
-    // cross into an unmapped page: it is read as the aligned dwords holding stream bytes (each
-    // inside its 128-B line) and funnelled to the stream's byte alignment by v_alignbyte
-    __device__ __forceinline__ void fetch_top(int32_t m, int32_t len) {
-        typedef __attribute__((address_space(1))) const uint32_t gu32;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(src) + 128ll * m;
-        const gu32* d0 = reinterpret_cast<const gu32*>(a & ~uintptr_t(3));
-        const uint32_t b = static_cast<uint32_t>(a & 3u);
-        const int32_t last = static_cast<int32_t>(((reinterpret_cast<uintptr_t>(src) + len - 1) >> 2) - (a >> 2));
-        uint32_t d[33];
-#pragma unroll
-        for (int q = 0; q < 33; ++q) d[q] = q <= last ? d0[q] : 0u;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            Q[k] = make_uint4(ab(d[4 * k + 1], d[4 * k], b), ab(d[4 * k + 2], d[4 * k + 1], b),
-                              ab(d[4 * k + 3], d[4 * k + 2], b), ab(d[4 * k + 4], d[4 * k + 3], b));
-    }
-    // W = bytes [P, P+4): ring rows (P>>2)&31 and the next (row 32 mirrors row 0).  With the
-    // ring base in the ds offsets the row address is one v_and_or of (P << 10) and the lane's column.
-    // The position is kept in bits (P8): renorm_up8 returns bit counts, and v_alignbit_b32 takes
-    // the window's bit offset 8 (P & 3) = P8 & 31 as it is.
-    uint32_t wx, wy, col;  // col = 4 * lane: the lane's byte column in the ring
-    __device__ __forceinline__ void read_window() {
-        // row (P>>2)&31: the mask first, then one v_lshl_or (a left shift by a constant issues
-        // at the slow rate, profiles/r02_valu_microbench.txt, and v_and_or would need it)
-        uint32_t a;
-        asm("v_lshl_or_b32 %0, %1, 7, %2" : "=v"(a) : "v"(static_cast<uint32_t>(P8) & 0x3E0u), "v"(col));
-        wy = lds_ld32(a + kDecTableBytes);
-        wx = lds_ld32(a + kDecTableBytes + 4 * kDecBlock);
-    }
-    // (v_alignbit_b32 reads only the low five bits of its shift operand: P8 needs no mask)
-    __device__ __forceinline__ void form_window() { W = __builtin_amdgcn_alignbit(wx, wy, static_cast<uint32_t>(P8)); }
-    // the top two pages land before decoding starts; the pair below them is requested.
-    // s: the stream's first byte, at any alignment (a dense container).  Positions count from s
-    // itself (sh = 0), so every lane's pages start at its own stream's start: streams of similar
-    // length then cross page boundaries at nearly the same symbols, in a dense container as in
-    // slots, and a wave runs the landing code about once per page rather than at every point
-    // (with pages at absolute 64-B boundaries the packed streams' random phases put some lane's
-    // landing at nearly every point: +2.2 VALU per symbol, profiles/r03_pmc_dense_vs_slot.txt).
-    __device__ __forceinline__ void start(const uint8_t* s, int32_t slen) {
-        sh = 0;
-        src = s;
-        const int32_t len = slen;
-        const int32_t top = len > 0 ? (len - 1) >> 6 : 0;
-        if (len > 0) fetch_top(top >> 1, len);
-        else fetch_pair(-1);
-        wait_vm();
-        put_page(top);
-        if (top & 1) {
-            put_page(top - 1);
-            fetch_pair((top >> 1) - 1);  // holds top-3, top-2
-        } else {
-            fetch_pair((top >> 1) - 1);  // holds top-2, top-1
-            wait_vm();
-            put_page(top - 1);  // top-2 stays in the low half
-        }
-        low = top - 1;
-        lim8 = 8 * (64 * low + 60);
-        P8 = 8 * (len - 4);
-        read_window();
-        head = 0;
-    }
-    // renorm_up one byte at a time (unflatten and the final equality check only)
-    __device__ __forceinline__ void pull_until(uint64_t bound) {
-        for (int g = 0; g < 9 && head < bound; ++g) {
-            form_window();
-            head = (head << 8) | (W >> 24);
-            P8 -= 8;
-            read_window();
-        }
-    }
-    // page low+1 is no longer read once ((P >> 2) + 1) >> 4 <= low, i.e. P < 64 low + 60
-    // (floor division throughout, negative positions included): one compare per point, in bits
-    int32_t lim8;  // 8 (64 low + 60)
-    __device__ __forceinline__ void point() {
-        if (P8 < lim8) {  // land the page below
-            put_page(low - 1);
-            --low;
-            lim8 -= 512;
-            if (!(low & 1)) fetch_pair((low >> 1) - 1);  // the next page (low-1, odd) opens a new pair
-        }
-    }
     // phase 1: renorm_up, q/cf, next window
     template <bool kJ4, int kNR = kNormStd>
     __device__ __forceinline__ void renorm_div(uint64_t L, uint32_t hL8, uint32_t norm, double rcp_norm,
                                                double neg_norm = 0.0) {
         form_window();
-        P8 -= static_cast<int32_t>(renorm_up8<kJ4>(head, W, L, hL8));
+        pos -= static_cast<int32_t>(renorm_up8<kJ4>(head, W, L, hL8));
         read_window();  // for the next step; kept ahead of this step's bucket reads
         __builtin_amdgcn_sched_barrier(0);
         div_norm<kNR>(head, norm, rcp_norm, qq, cf, neg_norm);
@@ -1032,7 +747,7 @@ struct DecChain {
     __device__ __forceinline__ void renorm_div_u(uint64_t L, uint32_t hL8, uint32_t norm, double rcp_norm, double rcp8,
                                                  double magic, double neg_norm = 0.0) {
         form_window();
-        P8 -= static_cast<int32_t>(renorm_up8<kJ4, kScreen>(head, W, L, hL8));
+        pos -= static_cast<int32_t>(renorm_up8<kJ4, kScreen>(head, W, L, hL8));
         read_window();  // for the next step; kept ahead of this step's bucket reads
         __builtin_amdgcn_sched_barrier(0);
         // 1/(8 norm) from its SGPR pair (an asm "v" operand copied it into a VGPR pair every step)
@@ -1284,7 +999,7 @@ __global__ __launch_bounds__(kDecBlock, 4) void k_decode(FastTable t, const uint
                         ch.point();
                         if constexpr (kDefer) {
                             h_pt = ch.head;
-                            p_pt = ch.P8;
+                            p_pt = ch.pos;
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -1323,7 +1038,7 @@ __global__ __launch_bounds__(kDecBlock, 4) void k_decode(FastTable t, const uint
                 if constexpr (kDefer) {
                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(hmax >= hL8) != 0, 0)) {
                         ch.head = h_pt;  // the unit again, with the per-step screen
-                        ch.P8 = p_pt;
+                        ch.pos = p_pt;
                         ch.read_window();
 #pragma unroll
                         for (int j = 0; j < U; ++j) {
@@ -1387,7 +1102,7 @@ __global__ __launch_bounds__(kDecBlock, 4) void k_decode(FastTable t, const uint
     }
     // assert_eq!(initial, m) with initial = the chunk's initial message (src/ans.rs:56, 302-310)
     ch.pull_until(kMaxMinHead);
-    const int32_t remaining = (ch.P8 >> 3) + 4 - ch.sh;  // < 0: generated
+    const int32_t remaining = ch.bytes_left();  // < 0: generated
     if (remaining < 0 && gen_kind == ANS_GEN_EMPTY) atomicOr(status, 1u << ANS_E_EXHAUSTED);
     else if (ch.head != ini.head(c) || remaining != 0) atomicOr(status, 1u << ANS_E_MISMATCH);
 }
@@ -1401,7 +1116,7 @@ __global__ __launch_bounds__(kDecBlock, 4) void k_decode(FastTable t, const uint
 // issued together at the block's point, which exposes one HBM latency per block instead of
 // one per unit.  The ring has four pages (65 rows, row 64 mirrors row 0); a block pops at most
 // 4U*KMAX <= 128 bytes, and up to two pages land per point, so reads never reach an unlanded
-// page.
+// page.  (A different ring from ans_ring.hpp's DecRingT, and not folded into it.)
 constexpr int kDecGRows = 65;
 constexpr uint32_t kDecGRingBytes = kDecGRows * kBlock * 4;
 

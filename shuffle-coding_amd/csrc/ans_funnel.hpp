@@ -27,7 +27,7 @@ ANS_FUNNEL_FN uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t s) {
 
 // the row bits of a ring address, (x << 6) & 0xF800 for x = 8 * (a stream position): dword
 // x >> 5 lives in ring row (x >> 5) & 31, and a row is 2^11 bytes of the [dword][lane] image.
-// On the device the shift is v_lshlrev_b16 (the five row bits come from x's bits 5..9; ans_fast.hpp
+// On the device the shift is v_lshlrev_b16 (the five row bits come from x's bits 5..9; ans_ring.hpp
 // shl16 has its cost)
 ANS_FUNNEL_FN uint32_t funnel_row(uint32_t x) {
 #if defined(__HIPCC__)
@@ -50,7 +50,7 @@ ANS_FUNNEL_FN uint32_t funnel_row(uint32_t x) {
 //   Z  = {lo:Z} >> 8 k         the window slides by k bytes
 // Every count is 0, 8, 16 or 24, exact in v_alignbit's five bits: b = 4 gives d0 = Z (the
 // complete dword rewritten with itself) and k = 0 leaves Z alone.  A count of 32 would wrap:
-// pushes of four bytes (KMAX = 4 tables) keep FunnelT (ans_fast.hpp).
+// pushes of four bytes (KMAX = 4 tables) keep FunnelT (ans_ring.hpp).
 //
 // Why the ring holds the stream: b >= 1 and k <= 3, so a push crosses at most one dword
 // boundary, and the dword it completes is the old current one, which d0 stores complete and

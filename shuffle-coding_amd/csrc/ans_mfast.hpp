@@ -51,7 +51,7 @@ using fast::wait_vm;
 
 constexpr int kLanes = 256;                       // chunks per workgroup
 constexpr uint32_t kEncRingBytes = 32 * kLanes * 4;  // 128-B ring per lane: 32 KiB
-constexpr uint32_t kDecRows = 33;                 // 32 ring rows + the mirror of row 0
+constexpr uint32_t kDecRows = fast::kDecRingRows;  // 32 ring rows + the mirror of row 0
 constexpr uint32_t kDecRingBytes = kDecRows * kLanes * 4;  // 33 KiB
 constexpr uint32_t kEncTab = kEncRingBytes;       // LDS offset of the encoder's model tables
 constexpr uint32_t kDecTab = kDecRingBytes;       // LDS offset of the decoder's model tables
@@ -65,12 +65,11 @@ constexpr uint64_t kMaxMinHead = 1ull << 56;  // src/ans.rs:19
 constexpr int kLanesW = 1024;
 constexpr uint32_t kDecTabW = 28672;
 static_assert(kDecTabW + kDecRows * kLanesW * 4 == kLdsMax, "1,024 rings + the tables = one CU's LDS");
+// (the ring's part of a layout is ans_ring.hpp's RingLayout: positions in bits, v_lshl_or rows)
 template <int kL>
-struct DecLayout {
+struct DecLayout : fast::RingLayout<kL, kL == kLanes ? 0u : kDecTabW, 8, fast::kRowLshlOr> {
     static_assert(kL == kLanes || kL == kLanesW, "two layouts");
-    static constexpr uint32_t kRing = kL == kLanes ? 0u : kDecTabW;   // LDS offset of ring row 0
     static constexpr uint32_t kTab = kL == kLanes ? kDecTab : 0u;     // LDS offset of the model's tables
-    static constexpr uint32_t kRowShift = kL == kLanes ? 10u : 12u;   // log2 of a ring row's bytes
     static constexpr uint32_t kLds = kL == kLanes ? 0u : kLdsMax;     // (256 lanes: the caller's size)
 };
 
@@ -88,117 +87,22 @@ constexpr uint32_t kErrPulled = 8;    // a take-back reached past the stream's s
 // R = log2 of a row's bytes.
 constexpr uint32_t kEncTabW = 32768;
 static_assert(kEncTabW + 32u * kLanesW * 4 == kLdsMax, "1,024 rings + the tables = one CU's LDS");
+// (256 lanes: ring addresses fit 16 bits, v_lshlrev_b16; 1,024: the mask first, then one v_lshl_or)
 template <int kL>
-struct EncLayout {
+struct EncLayout : fast::RingLayout<kL, kL == kLanes ? 0u : kEncTabW, 8, kL == kLanes ? fast::kRowShl16 : fast::kRowLshlOr7> {
     static_assert(kL == kLanes || kL == kLanesW, "two layouts");
-    static constexpr uint32_t kRing = kL == kLanes ? 0u : kEncTabW;
     static constexpr uint32_t kTab = kL == kLanes ? kEncTab : 0u;
-    static constexpr uint32_t kRowShift = kL == kLanes ? 10u : 12u;
-    static constexpr uint32_t kRowMask = 31u << kRowShift;
-    static_assert(kL == kLanes || kRowShift == 12, "row_of's shift: (pos8 & 0x3E0) << 7");
-    // the row address of stream bit position pos8 (dword pos8 >> 5), without the ring base
-    static __device__ __forceinline__ uint32_t row_of(uint32_t pos8, uint32_t col) {
-        if constexpr (kL == kLanes) {
-            return (shl16<5>(pos8) & kRowMask) | col;  // (fits 16 bits)
-        } else {  // the mask first, then one v_lshl_or (ans_fast.hpp DecChain::read_window)
-            uint32_t a;
-            asm("v_lshl_or_b32 %0, %1, 7, %2" : "=v"(a) : "v"(pos8 & 0x3E0u), "v"(col));
-            return a;
-        }
-    }
 };
-
-template <int kL>
-struct MRingT {
-    using Lay = EncLayout<kL>;
-    uint32_t col;
-    __device__ __forceinline__ lds_u32& at(int32_t i) const {
-        const uint32_t a = ((static_cast<uint32_t>(i) << Lay::kRowShift) & Lay::kRowMask) | col;
-        return *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(a + Lay::kRing));
-    }
-};
-
-// The byte funnel of ans_fast.hpp (FunnelT) on the ring, plus take_back: pos8 = 8 * stream bytes
-// so far; X holds dword pos/4 with its pos&3 written bytes at the bottom; every dword below it
-// is in the ring.  addr: the ring address (less the ring base) of dword pos/4.
-template <int kL>
-struct MFunnelT {
-    using Lay = EncLayout<kL>;
-    uint32_t X, pos8, neg8, addr, col;
-
-    __device__ __forceinline__ void push(uint32_t lo, uint32_t k8) {
-        uint32_t xv, d0, d1;
-        asm("v_bfe_u32 %0, %1, 0, %2" : "=v"(xv) : "v"(X), "v"(pos8));
-        asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(d0) : "v"(lo), "v"(pos8), "v"(xv));
-        asm("v_lshrrev_b32 %0, %1, %2" : "=v"(d1) : "v"(neg8), "v"(lo));
-        *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr + Lay::kRing)) = d0;
-        pos8 += k8;
-        neg8 -= k8;
-        const uint32_t a = Lay::row_of(pos8, col);
-        X = a != addr ? d1 : d0;
-        addr = a;
-    }
-    // the last byte back (renorm_up during a push, src/ans.rs:239-243); pos8 > 0
-    __device__ __forceinline__ uint32_t take_back() {
-        pos8 -= 8;
-        neg8 += 8;
-        const uint32_t a = Lay::row_of(pos8, col);
-        if (a != addr) {  // the byte lies in the dword below, which is in the ring
-            X = *reinterpret_cast<const lds_u32*>(static_cast<uintptr_t>(a + Lay::kRing));
-            addr = a;
-        }
-        return (X >> (pos8 & 31u)) & 0xFFu;
-    }
-    __device__ __forceinline__ uint32_t len() const { return pos8 >> 3; }
-    __device__ __forceinline__ void finish() {
-        uint32_t xv;
-        asm("v_bfe_u32 %0, %1, 0, %2" : "=v"(xv) : "v"(X), "v"(pos8));
-        *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(addr + Lay::kRing)) = xv;
-    }
-};
-
-// completed pages leave in aligned 128-B pairs (ans_fast.hpp PageOut)
-struct MPageOut {
-    uint4 h0, h1, h2, h3;
-    template <class Ring>
-    __device__ __forceinline__ void page(const Ring& ring, uint32_t p, uint8_t* dst) {
-        uint32_t w[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = ring.at(static_cast<int32_t>(16 * p + i));
-        const uint4 v0 = make_uint4(w[0], w[1], w[2], w[3]), v1 = make_uint4(w[4], w[5], w[6], w[7]);
-        const uint4 v2 = make_uint4(w[8], w[9], w[10], w[11]), v3 = make_uint4(w[12], w[13], w[14], w[15]);
-        if (p & 1) {
-            uint4* d = reinterpret_cast<uint4*>(dst + 64ull * (p - 1));
-            d[0] = h0;
-            d[1] = h1;
-            d[2] = h2;
-            d[3] = h3;
-            d[4] = v0;
-            d[5] = v1;
-            d[6] = v2;
-            d[7] = v3;
-        }
-        h0 = v0;
-        h1 = v1;
-        h2 = v2;
-        h3 = v3;
-    }
-    __device__ __forceinline__ void finish(uint32_t np, uint8_t* dst) {
-        if (np & 1) {
-            uint4* d = reinterpret_cast<uint4*>(dst + 64ull * (np - 1));
-            d[0] = h0;
-            d[1] = h1;
-            d[2] = h2;
-            d[3] = h3;
-        }
-    }
-};
+// the ring, the nine-VALU byte funnel (with take_back) and the page output are ans_ring.hpp's
+using fast::FunnelT;
+using fast::PageOut;
+using fast::RingT;
 
 // One chain's encoder state, handed to the model's push.
 template <int kL>
 struct EncLaneT {
     uint64_t head;
-    MFunnelT<kL> f;
+    FunnelT<EncLayout<kL>> f;
     uint32_t err;
     // push the head's low 8k8/8 bytes (up to 8) and drop them from the head
     __device__ __forceinline__ void emit(uint32_t k8) {
@@ -222,8 +126,6 @@ struct EncLaneT {
         }
     }
 };
-using MRing = MRingT<kLanes>;
-using MFunnel = MFunnelT<kLanes>;
 using EncLane = EncLaneT<kLanes>;
 
 // 8 * #{j >= 1 : head >> 8j >= pK} (src/ans.rs:246-253), exact (the voted slow paths)
@@ -284,7 +186,7 @@ __device__ __forceinline__ void unit_put(uint4& v, int j, uint32_t lo, uint32_t 
 //    codes those chunks after this kernel;
 //  * the position starts at the bytes left, not 0, with page fp = (pos - 1) / 64 (the first one
 //    not a byte behind the position: a take-back may reach byte pos - 1) loaded into the ring
-//    and, if fp is odd, its even partner into MPageOut's held page; the pages below stay
+//    and, if fp is odd, its even partner into PageOut's held page; the pages below stay
 //    untouched in the slot;
 //  * after the prologue the head is at least 2^56 and only grows until a push emits, so a
 //    take-back only ever returns a byte this call emitted: it never reaches below the start
@@ -325,11 +227,11 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, con
     const uint32_t npages_cap = static_cast<uint32_t>(slot_cap / 64);
     const int ngroups = static_cast<int>(chunk_len * sizeof(Sym) / (16 * GU));
 
-    const MRingT<kL> ring{4 * threadIdx.x};
-    MPageOut pout;
+    const RingT<EncLayout<kL>> ring{4 * threadIdx.x};
+    PageOut pout;
     EncLaneT<kL> e;
     e.head = ini.head(c);  // Message::zeros() / random(seed + c)
-    e.f = MFunnelT<kL>{0, 0, 0, ring.col, ring.col};
+    e.f = FunnelT<EncLayout<kL>>{0, 0, 0, ring.col, ring.col};
     e.err = 0;
     uint32_t fp = 0, over = 0;
     if constexpr (kRes) {
@@ -364,7 +266,7 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, con
         }
         // (dword pos / 4 with its pos & 3 bytes: the first dword of the next page when pos = 64 fp + 64,
         // none of whose bytes count)
-        e.f = MFunnelT<kL>{ring.at(static_cast<int32_t>(pos >> 2)), 8 * pos, 0u - 8 * pos,
+        e.f = FunnelT<EncLayout<kL>>{ring.at(static_cast<int32_t>(pos >> 2)), 8 * pos, 0u - 8 * pos,
                            EncLayout<kL>::row_of(8 * pos, ring.col), ring.col};
     }
     // page fp leaves once the position is a byte past it: a take-back never reaches a flushed page
@@ -479,11 +381,10 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_menc(Model md, con
 }
 
 // ====================================================================== decoder
-// The ans_fast.hpp DecChain on a 256-lane ring at LDS offset 0 (33 rows, row 32 mirrors row 0),
-// plus the renorm_down (push-back) of the bidirectional renorm and the two-round pull of codecs
-// whose pops can take more than four bytes (Uniform and LogUniform sizes up to 2^46).
-__device__ const uint4 kZeroPair[8] = {};  // the Zeros tail generator's bytes below a stream
-
+// The stream ring of ans_ring.hpp (DecRingT on DecLayout<kL>, positions in bits), plus the
+// renorm_down (push-back) of the bidirectional renorm and the two-round pull of codecs whose pops
+// can take more than four bytes (Uniform and LogUniform sizes up to 2^46).
+//
 // kRes: the chain of a resumed message (k_mdec<kRes>, ans_dev_independent_pop).  A byte that
 // renorm_down hands back is then new data, not the stream's own (the head of an unflattened
 // message was never a stream byte): it is STORED in the ring (and row 0's mirror) instead of
@@ -492,126 +393,20 @@ __device__ const uint4 kZeroPair[8] = {};  // the Zeros tail generator's bytes b
 // the ring to the slot (top_byte; the stream's own byte again when nothing is pending).  `bad`
 // there means a hand-back while the position was below byte 0: the Empty generator had been read.
 template <int kL, bool kRes = false>
-struct MChainT {
+struct MChainT : fast::DecRingT<DecLayout<kL>> {
     using Lay = DecLayout<kL>;
-    const uint8_t* src;
-    uint4 Q[8];
-    int32_t low, P8, lim8;
-    uint32_t W, wx, wy, col;
-    uint64_t head;
+    using Ring = fast::DecRingT<Lay>;
+    using Ring::form_window;
+    using Ring::head;
+    using Ring::pos;
+    using Ring::read_window;
+    using Ring::row_addr;
+    using Ring::W;
     bool bad;  // a pushed-back byte that differs from the stream's: corrupt (ANS_E_MISMATCH)
 
-    // sixteen ring rows from one address: rows kL * 4 bytes = kL / 64 st64 units apart
-    template <int R0>
-    __device__ __forceinline__ uint32_t put_half(uint4 a0, uint4 a1, uint4 a2, uint4 a3) {
-        constexpr int st = kL / 64;
-        const uint32_t base = col + Lay::kRing + R0 * kL * 4;
-        asm volatile(
-            "ds_write2st64_b32 %0, %1, %2 offset0:%17 offset1:%18\n\t"
-            "ds_write2st64_b32 %0, %3, %4 offset0:%19 offset1:%20\n\t"
-            "ds_write2st64_b32 %0, %5, %6 offset0:%21 offset1:%22\n\t"
-            "ds_write2st64_b32 %0, %7, %8 offset0:%23 offset1:%24\n\t"
-            "ds_write2st64_b32 %0, %9, %10 offset0:%25 offset1:%26\n\t"
-            "ds_write2st64_b32 %0, %11, %12 offset0:%27 offset1:%28\n\t"
-            "ds_write2st64_b32 %0, %13, %14 offset0:%29 offset1:%30\n\t"
-            "ds_write2st64_b32 %0, %15, %16 offset0:%31 offset1:%32"
-            :
-            : "v"(base), "v"(a0.x), "v"(a0.y), "v"(a0.z), "v"(a0.w), "v"(a1.x), "v"(a1.y), "v"(a1.z), "v"(a1.w),
-              "v"(a2.x), "v"(a2.y), "v"(a2.z), "v"(a2.w), "v"(a3.x), "v"(a3.y), "v"(a3.z), "v"(a3.w),
-              "i"(0), "i"(st), "i"(2 * st), "i"(3 * st), "i"(4 * st), "i"(5 * st), "i"(6 * st), "i"(7 * st),
-              "i"(8 * st), "i"(9 * st), "i"(10 * st), "i"(11 * st), "i"(12 * st), "i"(13 * st), "i"(14 * st),
-              "i"(15 * st)
-            : "memory");
-        return a0.x;
-    }
-    __device__ __forceinline__ void put_page(int32_t p) {
-        if (p & 1) {
-            put_half<16>(Q[4], Q[5], Q[6], Q[7]);
-        } else {
-            const uint32_t r0 = put_half<0>(Q[0], Q[1], Q[2], Q[3]);
-            *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(col + Lay::kRing + 32u * kL * 4)) = r0;  // mirror
-        }
-    }
-    __device__ __forceinline__ void fetch_pair(int32_t m) {
-        typedef __attribute__((address_space(1), aligned(1))) const fast::v4u32 gv4;
-        const uint4* g = m >= 0 ? reinterpret_cast<const uint4*>(src + 128ll * m) : kZeroPair;
-        const gv4* gg = reinterpret_cast<const gv4*>(reinterpret_cast<uintptr_t>(g));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const fast::v4u32 v = gg[k];
-            Q[k] = make_uint4(v.x, v.y, v.z, v.w);
-        }
-    }
-    // the top pair as the aligned dwords holding stream bytes (no read past the stream's line)
-    __device__ __forceinline__ void fetch_top(int32_t m, int32_t len) {
-        typedef __attribute__((address_space(1))) const uint32_t gu32;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(src) + 128ll * m;
-        const gu32* d0 = reinterpret_cast<const gu32*>(a & ~uintptr_t(3));
-        const uint32_t b = static_cast<uint32_t>(a & 3u);
-        const int32_t last = static_cast<int32_t>(((reinterpret_cast<uintptr_t>(src) + len - 1) >> 2) - (a >> 2));
-        uint32_t d[33];
-#pragma unroll
-        for (int q = 0; q < 33; ++q) d[q] = q <= last ? d0[q] : 0u;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            Q[k] = make_uint4(ab(d[4 * k + 1], d[4 * k], b), ab(d[4 * k + 2], d[4 * k + 1], b),
-                              ab(d[4 * k + 3], d[4 * k + 2], b), ab(d[4 * k + 4], d[4 * k + 3], b));
-    }
-    // ring row (P8 >> 5) & 31 of the lane's column (the ring base added by the caller / offsets)
-    __device__ __forceinline__ uint32_t row_addr(int32_t p8) const {
-        uint32_t a;
-        asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(static_cast<uint32_t>(p8) & 0x3E0u), "i"(Lay::kRowShift - 5), "v"(col));
-        return a;
-    }
-    // W = stream bytes [P, P+4): ring rows (P>>2)&31 and the next; P8 = 8P
-    __device__ __forceinline__ void read_window() {
-        const uint32_t a = row_addr(P8);
-        wy = lds_ld32(a + Lay::kRing);
-        wx = lds_ld32(a + Lay::kRing + 4 * kL);
-    }
-    __device__ __forceinline__ void form_window() { W = __builtin_amdgcn_alignbit(wx, wy, static_cast<uint32_t>(P8)); }
-    // the byte just below the position (stream byte P + 3, the window's top), as the ring holds it
-    __device__ __forceinline__ uint32_t top_byte() const {
-        const int32_t p8 = P8 + 24;
-        return (lds_ld32(row_addr(p8) + Lay::kRing) >> (static_cast<uint32_t>(p8) & 24u)) & 0xFFu;
-    }
     __device__ __forceinline__ void start(const uint8_t* s, int32_t len) {
-        src = s;
         bad = false;
-        const int32_t top = len > 0 ? (len - 1) >> 6 : 0;
-        if (len > 0) fetch_top(top >> 1, len);
-        else fetch_pair(-1);
-        wait_vm();
-        put_page(top);
-        if (top & 1) {
-            put_page(top - 1);
-            fetch_pair((top >> 1) - 1);
-        } else {
-            fetch_pair((top >> 1) - 1);
-            wait_vm();
-            put_page(top - 1);
-        }
-        low = top - 1;
-        lim8 = 8 * (64 * low + 60);
-        P8 = 8 * (len - 4);
-        read_window();
-        head = 0;
-    }
-    __device__ __forceinline__ void pull_until(uint64_t bound) {
-        for (int g = 0; g < 9 && head < bound; ++g) {
-            form_window();
-            head = (head << 8) | (W >> 24);
-            P8 -= 8;
-            read_window();
-        }
-    }
-    __device__ __forceinline__ void point() {
-        if (P8 < lim8) {
-            put_page(low - 1);
-            --low;
-            lim8 -= 512;
-            if (!(low & 1)) fetch_pair((low >> 1) - 1);
-        }
+        Ring::start(s, len);
     }
     // renorm(L) (src/ans.rs:233-253) from the window W: head = head << 8k | the top k bytes of W for
     // the least k in 0..4 that reaches L (ans_fast.hpp renorm_up8: byte permutes from the clz),
@@ -641,13 +436,13 @@ struct MChainT {
                 head = mk64(xm1, xm0);
                 m8 -= 8;
                 if (m == 0) {  // renorm_down: byte xj0 & 0xFF back onto the stream at P + 4
-                    const int32_t p8 = P8 + 32;
+                    const int32_t p8 = pos + 32;
                     if constexpr (kRes) {
                         const uint32_t a = row_addr(p8) + Lay::kRing, sh = static_cast<uint32_t>(p8) & 24u;
                         const uint32_t d = (lds_ld32(a) & ~(0xFFu << sh)) | ((xj0 & 0xFFu) << sh);
                         *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(a)) = d;
                         if ((static_cast<uint32_t>(p8) & 0x3E0u) == 0)  // row 0: its mirror too
-                            *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(col + Lay::kRing + 32u * kL * 4)) = d;
+                            *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>(this->mirror_addr())) = d;
                         bad |= p8 < 0;
                     } else {
                         const uint32_t byte = (lds_ld32(row_addr(p8) + Lay::kRing) >> (static_cast<uint32_t>(p8) & 31u)) & 0xFFu;
@@ -661,12 +456,12 @@ struct MChainT {
     // renorm to L for heads that may need more than four bytes (a second round, voted)
     __device__ __forceinline__ void renorm_wide(uint64_t L, uint32_t hL8) {
         form_window();
-        P8 -= renorm_up8(L, hL8);
+        pos -= renorm_up8(L, hL8);
         read_window();
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(head < L) != 0, 0)) {
             if (head < L) {
                 form_window();
-                P8 -= renorm_up8(L, hL8);
+                pos -= renorm_up8(L, hL8);
                 read_window();
             }
         }
@@ -723,7 +518,7 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, con
     const uint64_t bound0 = md.first_bound(tsrc);
     ch.pull_until(bound0);  // Message::unflatten: head 0, the first pop's renorm_up
     if constexpr (kRes) {
-        if (ch.head < bound0 || ch.P8 < -32) {
+        if (ch.head < bound0 || ch.pos < -32) {
             const_cast<uint32_t*>(lens)[c] = lens[c] | kResumeExact;
             return;
         }
@@ -843,7 +638,10 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, con
     if constexpr (kRes) {
         uint32_t* const lens_out = const_cast<uint32_t*>(lens);
         uint8_t* const slot = const_cast<uint8_t*>(ch.src);  // (offsets == NULL: slots + c * slot_cap)
-        const int32_t rem = (ch.P8 >> 3) + 4;  // bytes of the stream left; < 0: the generator was read
+        // bytes of the stream left (ch.bytes_left(), written out: through the member the compiler folds the
+        // + 4 into the compares below differently, and this epilogue's instruction stream changes); < 0: the
+        // generator was read
+        const int32_t rem = (ch.pos >> 3) + 4;
         const uint32_t nb = (71u - static_cast<uint32_t>(__builtin_clzll(ch.head | 1))) >> 3;  // head bytes, >= 1
         if (rem < 0 || ch.bad) {
             atomicOr(status, 1u << ANS_E_EXHAUSTED);
@@ -860,7 +658,7 @@ __global__ __launch_bounds__(kL, kL == kLanes ? 2 : 1) void k_mdec(Model md, con
     }
     // assert_eq!(initial, m) (src/ans.rs:56, 302-310)
     ch.pull_until(kMaxMinHead);
-    const int32_t remaining = (ch.P8 >> 3) + 4;  // < 0: generated
+    const int32_t remaining = ch.bytes_left();  // < 0: generated
     if (remaining < 0 && gen_kind == ANS_GEN_EMPTY) atomicOr(status, 1u << ANS_E_EXHAUSTED);
     else if (ch.bad || md.dec_bad(ds) || ch.head != ini.head(c) || remaining != 0) atomicOr(status, 1u << ANS_E_MISMATCH);
 }
@@ -1054,7 +852,7 @@ struct IndepModel {
         // bracket around the row read gained nothing)
         __builtin_amdgcn_s_setprio(2);
         ch.form_window();
-        ch.P8 -= ch.template renorm_up8<!kLean>(L, kScreenAll);
+        ch.pos -= ch.template renorm_up8<!kLean>(L, kScreenAll);
         ch.read_window();  // for the next pop
         __builtin_amdgcn_sched_barrier(0);
         uint64_t qq;
@@ -1234,7 +1032,7 @@ struct LogUniformModel {
         if (bits != 0) {
             st.bad |= bits > 47;  // no valid stream holds such a count (the encoder refuses it)
             ch.form_window();
-            ch.P8 -= ch.renorm_up8(kMaxMinHead, 0xFFFFFFFFu);  // renorm(2^(bits-1) * 2^(57-bits)) = 2^56
+            ch.pos -= ch.renorm_up8(kMaxMinHead, 0xFFFFFFFFu);  // renorm(2^(bits-1) * 2^(57-bits)) = 2^56
             ch.read_window();
             const uint32_t sh = min(bits, 48u) - 1u;
             x = (ch.head & ((1ull << sh) - 1ull)) | (1ull << sh);

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kBlock, 2) void k_encode_w(FastTable t, const Sym* 
             for (uint32_t i = threadIdx.x; i < kWideSaBytes / 4; i += kBlock) ls[i] = t.enc_sa_img[i];
         }
     }
-    const RingT<Lay::ring> ring{4 * threadIdx.x};
+    const RingT<EncLay<Lay::ring>> ring{4 * threadIdx.x};
     __syncthreads();
     const uint64_t c = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (c >= nfull) return;
@@ -147,8 +147,8 @@ __global__ __launch_bounds__(kBlock, 2) void k_encode_w(FastTable t, const Sym* 
     const uint32_t* gcum = t.cum;
 
     uint64_t head = ini.head(c);  // Message::zeros() / random(seed + c)
-    FunnelT<Lay::ring> f{0, 0, 0, ring.col, ring.col};
-    PageOut<Lay::ring> pout;
+    FunnelT<EncLay<Lay::ring>> f{0, 0, 0, ring.col, ring.col};
+    PageOut pout;
     uint32_t fp = 0, over = 0;
     uint32_t minmass = ~0u;
 
@@ -379,152 +379,33 @@ __global__ __launch_bounds__(kBlock, 2) void k_encode_w(FastTable t, const Sym* 
 //    (three ds_read2_b32) resolve four candidates; cf >= cdf(s0+4) scans the staged cdf (voted);
 //  * otherwise the global DecBucketG of cf >> dec_shift (cdf(s0..s0+5) and s0, 32 B in one
 //    128-B line: one L2 request), with the global cdf scan past its fifth candidate (voted).
-// The stream ring holds two 64-B pages per lane (33 rows x 512 lanes, row 32 mirroring row 0);
-// the next aligned 128-B page pair waits in registers and lands one page per point.  A point
-// comes every 16 symbols (at most 64 B, KMAX <= 4), so reads never reach an unlanded page, and
-// one global page fetch per 128 B exposes its HBM latency once per ~64 symbols (gfx9 retires
-// vector-memory operations in issue order, so a page fetch delays the next bucket load).
-constexpr int kWideDecRows = 33;
+// The stream ring is ans_ring.hpp's DecRingT on 512 lanes at LDS offset 0 (two 64-B pages per
+// lane, positions in bytes): the next aligned 128-B page pair waits in registers and lands one
+// page per point.  A point comes every 16 symbols (at most 64 B, KMAX <= 4), so reads never
+// reach an unlanded page, and one global page fetch per 128 B exposes its HBM latency once per
+// ~64 symbols (gfx9 retires vector-memory operations in issue order, so a page fetch delays the
+// next bucket load).
+constexpr int kWideDecRows = kDecRingRows;
 // 512 lanes: 1,024 (four waves per SIMD, 25 KiB of tables) measured 40% slower on C4, its
 // smaller LDS prefix sending more lookups to L2
 constexpr uint32_t kWideDecLanes = 512;
-constexpr uint32_t kWideDecRowShift = 11;  // log2 of a ring row's bytes
-static_assert((1u << kWideDecRowShift) == kWideDecLanes * 4, "row bytes");
 constexpr uint32_t kWideDecTab = kWideDecRows * kWideDecLanes * 4;  // 67,584 B of ring, then the tables
 static_assert(kWideDecTab % 256 == 0, "table base");
 constexpr uint32_t kWideDecTabBytes = 160u * 1024u - kWideDecTab;
 constexpr uint32_t kWideDecBktLds = kWideDecTabBytes / 16;  // compact buckets staged beside the ring
-__device__ const uint4 kZeroPair[8] = {};  // 128 zero bytes: pages below the stream start
+// (all 32 rows of 512 lanes fit the landing's st64 offset fields: it stores from col itself)
+using WideDecLay = RingLayout<kWideDecLanes, 0, 1, kRowPlain, true>;
 
-struct DecChainW {
-    uint32_t col;  // 4 * lane
-    const uint8_t* src;
-    uint4 Q[8];    // the page pair (2m, 2m+1) not yet landed
-    int32_t low, P, sh;  // sh: the stream start within its 128-B line
-    uint32_t wx, wy, W;
-    uint64_t head;
+struct DecChainW : DecRingT<WideDecLay> {
     uint64_t qq;
     uint32_t cf, cum, nxt, sx;
     bool far;
 
-    __device__ __forceinline__ lds_u32& row(int32_t r) const {
-        return *reinterpret_cast<lds_u32*>(static_cast<uintptr_t>((static_cast<uint32_t>(r) << kWideDecRowShift) + col));
-    }
-    // positions count from the stream's first byte (ans_fast.hpp DecChain::fetch_pair): pairs
-    // below the top one lie inside the stream and are read with unaligned 16-B loads
-    __device__ __forceinline__ void fetch_pair(int32_t m) {
-        typedef __attribute__((address_space(1), aligned(1))) const v4u32 gv4;
-        const uint4* g = m >= 0 ? reinterpret_cast<const uint4*>(src + 128ll * m) : kZeroPair;
-        const gv4* gg = reinterpret_cast<const gv4*>(reinterpret_cast<uintptr_t>(g));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const v4u32 v = gg[k];
-            Q[k] = make_uint4(v.x, v.y, v.z, v.w);
-        }
-    }
-    // page p (its half of Q) into ring slot p & 1: eight ds_write2st64_b32 from the lane's
-    // column (rows 2 KiB apart are 8 st64 units, rows 0..31 within the 8-bit offset fields);
-    // pages count from the stream's start, so none holds another stream's bytes
-    template <int R0>
-    __device__ __forceinline__ void land_half(uint4 a0, uint4 a1, uint4 a2, uint4 a3) {
-        constexpr int o = 8 * R0;
-        asm volatile(
-            "ds_write2st64_b32 %0, %1, %2 offset0:%17 offset1:%18\n\t"
-            "ds_write2st64_b32 %0, %3, %4 offset0:%19 offset1:%20\n\t"
-            "ds_write2st64_b32 %0, %5, %6 offset0:%21 offset1:%22\n\t"
-            "ds_write2st64_b32 %0, %7, %8 offset0:%23 offset1:%24\n\t"
-            "ds_write2st64_b32 %0, %9, %10 offset0:%25 offset1:%26\n\t"
-            "ds_write2st64_b32 %0, %11, %12 offset0:%27 offset1:%28\n\t"
-            "ds_write2st64_b32 %0, %13, %14 offset0:%29 offset1:%30\n\t"
-            "ds_write2st64_b32 %0, %15, %16 offset0:%31 offset1:%32"
-            :
-            : "v"(col), "v"(a0.x), "v"(a0.y), "v"(a0.z), "v"(a0.w), "v"(a1.x), "v"(a1.y), "v"(a1.z), "v"(a1.w),
-              "v"(a2.x), "v"(a2.y), "v"(a2.z), "v"(a2.w), "v"(a3.x), "v"(a3.y), "v"(a3.z), "v"(a3.w),
-              "i"(o), "i"(o + 8), "i"(o + 16), "i"(o + 24), "i"(o + 32), "i"(o + 40), "i"(o + 48), "i"(o + 56),
-              "i"(o + 64), "i"(o + 72), "i"(o + 80), "i"(o + 88), "i"(o + 96), "i"(o + 104), "i"(o + 112), "i"(o + 120)
-            : "memory");
-    }
-    __device__ __forceinline__ void land(int32_t p) {
-        if (p & 1) {
-            land_half<16>(Q[4], Q[5], Q[6], Q[7]);
-        } else {
-            land_half<0>(Q[0], Q[1], Q[2], Q[3]);
-            row(32) = Q[0].x;  // row 32 mirrors row 0
-        }
-    }
-    __device__ __forceinline__ void read_window() {
-        const uint32_t a = ((static_cast<uint32_t>(P) << (kWideDecRowShift - 2)) & (31u << kWideDecRowShift)) | col;  // row (P >> 2) & 31
-        wy = *reinterpret_cast<const lds_u32*>(static_cast<uintptr_t>(a));
-        wx = *reinterpret_cast<const lds_u32*>(static_cast<uintptr_t>(a + kWideDecLanes * 4));
-    }
-    __device__ __forceinline__ void form_window() { W = ab(wx, wy, static_cast<uint32_t>(P)); }
-    // the top pair, which may reach past the stream's end: the aligned dwords holding stream
-    // bytes, funnelled to the stream's alignment (ans_fast.hpp DecChain::fetch_top)
-    __device__ __forceinline__ void fetch_top(int32_t m, int32_t len) {
-        typedef __attribute__((address_space(1))) const uint32_t gu32;
-        const uintptr_t a = reinterpret_cast<uintptr_t>(src) + 128ll * m;
-        const gu32* d0 = reinterpret_cast<const gu32*>(a & ~uintptr_t(3));
-        const uint32_t b = static_cast<uint32_t>(a & 3u);
-        const int32_t last = static_cast<int32_t>(((reinterpret_cast<uintptr_t>(src) + len - 1) >> 2) - (a >> 2));
-        uint32_t d[33];
-#pragma unroll
-        for (int q = 0; q < 33; ++q) d[q] = q <= last ? d0[q] : 0u;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            Q[k] = make_uint4(ab(d[4 * k + 1], d[4 * k], b), ab(d[4 * k + 2], d[4 * k + 1], b),
-                              ab(d[4 * k + 3], d[4 * k + 2], b), ab(d[4 * k + 4], d[4 * k + 3], b));
-    }
-    // the top two pages land before decoding starts; the pair below them is requested.
-    // s: the stream's first byte, at any alignment (a dense container); positions count from s
-    // itself (sh = 0), so the lanes of a wave land pages at nearly the same symbols in a dense
-    // container as in slots (ans_fast.hpp DecChain::start)
-    __device__ __forceinline__ void start(const uint8_t* s, int32_t slen) {
-        sh = 0;
-        src = s;
-        const int32_t len = slen;
-        const int32_t top = len > 0 ? (len - 1) >> 6 : 0;
-        if (len > 0) fetch_top(top >> 1, len);
-        else fetch_pair(-1);
-        wait_vm();
-        land(top);
-        if (top & 1) {
-            land(top - 1);
-            fetch_pair((top >> 1) - 1);  // holds top-3, top-2
-        } else {
-            fetch_pair((top >> 1) - 1);  // holds top-2, top-1
-            wait_vm();
-            land(top - 1);                // top-2 stays in the low half
-        }
-        low = top - 1;
-        lim = 64 * low + 60;
-        P = len - 4;
-        read_window();
-        head = 0;
-    }
-    __device__ __forceinline__ void pull_until(uint64_t bound) {
-        for (int g = 0; g < 9 && head < bound; ++g) {
-            form_window();
-            head = (head << 8) | (W >> 24);
-            P -= 1;
-            read_window();
-        }
-    }
-    // at a point (after s_waitcnt vmcnt(0)): land page low-1 once page low+1 is no longer read
-    // (((P >> 2) + 1) >> 4 <= low  <=>  P < lim = 64 low + 60: one compare per point)
-    int32_t lim;
-    __device__ __forceinline__ void point() {
-        if (P < lim) {
-            land(low - 1);
-            --low;
-            lim -= 64;
-            if (!(low & 1)) fetch_pair((low >> 1) - 1);  // the next page (low-1, odd) opens a new pair
-        }
-    }
     template <int kNR = kNormStd>
     __device__ __forceinline__ void renorm_div(uint64_t L, uint32_t hL8, uint32_t norm, double rcp_norm,
                                                double neg_norm = 0.0) {
         form_window();
-        P -= static_cast<int32_t>(renorm_up(head, W, L, hL8));
+        pos -= static_cast<int32_t>(renorm_up(head, W, L, hL8));
         read_window();  // for the next step; kept ahead of this step's lookups
         __builtin_amdgcn_sched_barrier(0);
         div_norm<kNR>(head, norm, rcp_norm, qq, cf, neg_norm);
@@ -763,7 +644,7 @@ __global__ __launch_bounds__(kWideDecLanes, 2) void k_decode_w(FastTable t, cons
     }
     // assert_eq!(initial, m) with initial = the chunk's initial message (src/ans.rs:56, 302-310)
     ch.pull_until(kMaxMinHead);
-    const int32_t remaining = ch.P + 4 - ch.sh;  // < 0: generated
+    const int32_t remaining = ch.bytes_left();  // < 0: generated
     if (remaining < 0 && gen_kind == ANS_GEN_EMPTY) atomicOr(status, 1u << ANS_E_EXHAUSTED);
     else if (ch.head != ini.head(c) || remaining != 0) atomicOr(status, 1u << ANS_E_MISMATCH);
 }

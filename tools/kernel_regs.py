@@ -16,13 +16,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B = "/opt/rocm/lib/llvm/bin"
 
 
+def code_object(obj, tmpdir):
+    """The gfx950 code object bundled in a HIP object file, unbundled into tmpdir."""
+    subprocess.check_call([f"{B}/llvm-objcopy", f"--dump-section=.hip_fatbin={tmpdir}/f.bin", obj])
+    subprocess.check_call([f"{B}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={tmpdir}/f.bin",
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={tmpdir}/k.co"])
+    return f"{tmpdir}/k.co"
+
+
 def notes(unit):
     with tempfile.TemporaryDirectory() as t:
-        subprocess.check_call([f"{B}/llvm-objcopy", f"--dump-section=.hip_fatbin={t}/f.bin",
-                               os.path.join(ROOT, "shuffle-coding_amd", "build", unit + ".o")])
-        subprocess.check_call([f"{B}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={t}/f.bin",
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={t}/k.co"])
-        return subprocess.check_output([f"{B}/llvm-readelf", "--notes", f"{t}/k.co"], text=True)
+        co = code_object(os.path.join(ROOT, "shuffle-coding_amd", "build", unit + ".o"), t)
+        return subprocess.check_output([f"{B}/llvm-readelf", "--notes", co], text=True)
 
 
 def main():
