@@ -122,6 +122,29 @@ int ans_pop_iid(ans_msg *m, const ans_table *t, uint32_t *out, size_t n);
 uint64_t ans_orbit_id(uint64_t x);
 int ans_mset_push(ans_msg *m, const ans_table *t, const uint32_t *syms, size_t n);
 int ans_mset_pop(ans_msg *m, const ans_table *t, uint32_t *out, size_t n);
+/* The Pólya urn model of one undirected graph's edge set: multiset_shuffle_codec(
+ * PolyaUrnEdgeIndicesCodec<Undirected>{num_nodes, num_edges, loops, redraws}), the harness's
+ * polya_urn(n, E, loops, redraws)  src/graph_codec.rs:210-375, src/recursive/multiset.rs:126-136.
+ * edges: num_edges distinct uint32 pairs (i, j) with i <= j < num_nodes (the alphabet of section 5);
+ * fewer than 2^31 of them.  The order of the pairs does not matter to push.
+ *   push: E <= 11 is plain_shuffle_codec (src/plain/mod.rs:111-116): the pairs sorted as tuples, a
+ *         permutation POPPED by PermutationUniform{E}, the permuted vector pushed by the ordered
+ *         codec.  E >= 12 is the joint recursive codec (src/recursive/mod.rs:117-134, joint.rs):
+ *         for L = E .. 1 an orbit is popped under the L pairs left (orbit id = hash((i, j)), every
+ *         orbit a singleton) and swapped to position L - 1; then the ordered push.
+ *         The ordered codec (src/graph_codec.rs:318-326) removes the pairs last to first; each is
+ *         pushed by the per-edge plain shuffle (:269-276) under the urn over the nodes with mass
+ *         degree + 1: the second node with the first node's own mass taken out unless `loops`, and
+ *         its current neighbours' unless `redraws`; then the first node.
+ *   pop:  the inverse.  E <= 11 returns the pairs sorted, E >= 12 in pop order (deterministic).
+ * ANS_E_SYMBOL: i > j, a node >= num_nodes, a loop without `loops`, a pair given (or decoded) twice.
+ * ANS_E_ZERO_MASS: a pop whose urn is empty after the exclusions.  ANS_E_EXHAUSTED: as ans_cat_pop.
+ * ANS_E_ARG: 2^31 or more pairs, or two different pairs with one orbit id (not built).
+ * The orbit id is SipHash-1-3, keys 0, 0, over the two usizes' 16 bytes (csrc/ans_polya.hpp edge_id).
+ * A failed call leaves the message wherever the failing step found it.  Directed graphs are not
+ * coded (the reference asserts !is_directed, :220). */
+int ans_polya_push(ans_msg *m, uint32_t num_nodes, int loops, int redraws, const uint32_t *edges, size_t num_edges);
+int ans_polya_pop(ans_msg *m, uint32_t num_nodes, int loops, int redraws, uint32_t *edges, size_t num_edges);
 
 /* ======================================================================
  * (4) GPU bulk path (MI355X / gfx950) — the data-parallel hot path.
@@ -179,9 +202,10 @@ int ans_gpu_table_paths(const ans_gpu_table *gt, uint32_t *paths);
  *   k_menc<indep,u8,spp=16,lanes=256,res=0,rare=0,nr=std>   k_mdec<indep,u8,spp=16,lanes=256,res=0,lean=1,nr=std>
  *   k_encode64<catset,u8>   k_decode64<catset,u8>   k_push64<u8>   k_pop64<u8>
  *   k_mset_push<u8,cnt=lds>   k_mset_pop<u16,cnt=global>      (cnt: where the per-lane counts live)
+ *   k_polya_push<redraws=0>   k_polya_pop<redraws=1>          (section 5c)
  * The calls that write it are the Categorical table's (sections 3 and 4: fixed, ragged and variable
  * chunks, host or device buffers; a pipelined host call leaves its last batch's launches), the
- * Independent ones (new messages and resume) and the multiset ones; helper kernels (staging, compaction) are not named,
+ * Independent ones (new messages and resume), the multiset ones and the Pólya urn ones; helper kernels (staging, compaction) are not named,
  * and the other calls (and calls that return before any launch: no symbols, bad arguments) leave
  * the record as it was.  Empty before the first such call.
  * Writes *len = the text's bytes (without the terminating NUL) and, if cap > *len, the
@@ -629,6 +653,51 @@ int ans_gpu_graphs_decode(ans_gpu_tableset *ts, uint32_t node_table, uint32_t ed
                           const uint32_t *num_nodes, const uint8_t *in, uint64_t in_len, const uint64_t *offsets,
                           const uint64_t *lens, int gen_kind, uint64_t seed, uint32_t *node_labels, uint32_t *edges,
                           uint32_t *edge_labels, uint64_t cap, uint64_t *edge_offsets);
+
+/* ======================================================================
+ * (5c) The Pólya urn edge-index codec in bulk: ans_polya_push / ans_polya_pop (section 3) of graph
+ *      g's edges onto / from the message ALREADY in slot g, one lane per graph, under the resume
+ *      contract of section 4b word for word: the input is Message::unflatten(slot bytes, d_lens[g])
+ *      with the Empty tail, the result is flattened back into the slot and d_lens[g] is its length
+ *      (a graph without edges grows by the one 0x00 of flatten).  The bytes equal the host codec's.
+ *      Graph g has d_num_nodes[g] nodes and the pairs [d_edge_offsets[g], d_edge_offsets[g+1]) of
+ *      d_edges (num_graphs + 1 offsets; pop WRITES the pairs there: the caller supplies the offsets,
+ *      E being a parameter of the model).  With push after ans_dev_independent_push_var of the edge
+ *      labels and before that of the node labels, slot g holds GraphIID<NodeC, EdgeC, PolyaUrn>.
+ *      Statuses are OR-ed into *d_status with d_lens[g] = 0 for that graph alone: those of
+ *      ans_polya_push / _pop; ANS_E_ARG for a graph of more than max_nodes nodes or max_edges edges;
+ *      ANS_E_LEN for a result past slot_cap or a d_lens[g] above it.  With slot_cap >= d_lens[g] +
+ *      ans_gpu_polya_slack(max_nodes, max_edges) neither call meets ANS_E_LEN: the slack is
+ *      (max_edges / 8 + 1) * max(2 bitlen(max_nodes + 2 max_edges), bitlen(max_edges) + 1)
+ *      + max_edges / 2^20 + 16 bytes (a push adds two urn symbols per edge, a pop puts an orbit
+ *      and an orientation bit back).  The host-buffer calls apply it themselves.
+ *      The per-lane state (2 max_nodes + 6 max_edges + 2 dwords) lives in the workspace the
+ *      multiset kernels' cnt=global form uses, which calls on one context therefore must not share
+ *      between streams running at the same time; it is sized by the lanes resident, at most
+ *      256 MiB, and max_nodes / max_edges whose single wave passes that are ANS_E_ARG, as are
+ *      max_edges >= 2^31.  Kernel names in ans_gpu_last_launch: k_polya_push<redraws=0>,
+ *      k_polya_pop<redraws=1>.
+ * ====================================================================== */
+int ans_gpu_polya_slack(uint32_t max_nodes, uint64_t max_edges, uint64_t *bytes);
+int ans_dev_polya_push(ans_gpu *g, int loops, int redraws, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                       const uint32_t *d_edges, const uint64_t *d_edge_offsets, uint32_t max_nodes,
+                       uint64_t max_edges, uint8_t *d_slots, uint64_t slot_cap, uint32_t *d_lens /* in/out */,
+                       uint32_t *d_status, void *stream);
+int ans_dev_polya_pop(ans_gpu *g, int loops, int redraws, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                      uint32_t *d_edges /* out */, const uint64_t *d_edge_offsets, uint32_t max_nodes,
+                      uint64_t max_edges, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                      uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, a dense container in and one out exactly as
+ * ans_gpu_mset_push_var_chunks / _pop_var_chunks (out == NULL is the size query; pop still fills
+ * out_edges, edge_offsets[num_graphs] pairs). */
+int ans_gpu_polya_push_graphs(ans_gpu *g, int loops, int redraws, uint64_t num_graphs, const uint32_t *num_nodes,
+                              const uint32_t *edges, const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                              const uint64_t *in_offsets, const uint64_t *in_lens, uint8_t *out, uint64_t out_cap,
+                              uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_polya_pop_graphs(ans_gpu *g, int loops, int redraws, uint64_t num_graphs, const uint32_t *num_nodes,
+                             const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                             const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges, uint8_t *out,
+                             uint64_t out_cap, uint64_t *offsets, uint64_t *lens, uint64_t *total);
 
 #ifdef __cplusplus
 }

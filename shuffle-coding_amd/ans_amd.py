@@ -150,6 +150,13 @@ SIGNATURES = {
     "ans_orbit_id": (u64, [u64]),
     "ans_mset_push": (ci, [vp, vp, vp, sz]),
     "ans_mset_pop": (ci, [vp, vp, vp, sz]),
+    "ans_polya_push": (ci, [vp, ctypes.c_uint32, ci, ci, vp, sz]),
+    "ans_polya_pop": (ci, [vp, ctypes.c_uint32, ci, ci, vp, sz]),
+    "ans_gpu_polya_slack": (ci, [ctypes.c_uint32, u64, u64p]),
+    "ans_dev_polya_push": (ci, [vp, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_dev_polya_pop": (ci, [vp, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_gpu_polya_push_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_polya_pop_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
     "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
     "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
@@ -645,6 +652,42 @@ class MultisetShuffle(Codec):
         _, mult = np.unique(np.asarray(x, dtype=np.uint64), return_counts=True)
         order = math.lgamma(len(x) + 1) - sum(math.lgamma(int(c) + 1) for c in mult)
         return total - order / math.log(2)
+
+
+def _edge_pairs(edges):
+    return np.ascontiguousarray(np.asarray(edges, dtype=np.uint32).reshape(-1, 2))
+
+
+class PolyaUrn(Codec):
+    """polya_urn(num_nodes, num_edges, loops, redraws) of src/graph_codec.rs:373-375 for undirected
+    graphs: multiset_shuffle_codec(PolyaUrnEdgeIndicesCodec), on the host through ans_polya_push /
+    ans_polya_pop.  A symbol is the graph's edges as pairs (i, j), i <= j; pop returns them as an
+    Unordered of tuples."""
+
+    def __init__(self, num_nodes, num_edges, loops, redraws, directed=False):
+        if directed:  # the reference asserts !is_directed, src/graph_codec.rs:220
+            raise AnsError(ANS_E_ARG, "PolyaUrn: directed graphs are not coded")
+        self.num_nodes, self.num_edges, self.loops, self.redraws = num_nodes, num_edges, bool(loops), bool(redraws)
+
+    def push(self, m, x):
+        e = _edge_pairs(list(x))
+        assert len(e) == self.num_edges  # src/graph_codec.rs:319
+        _check(lib().ans_polya_push(m.h, self.num_nodes, self.loops, self.redraws, _np_ptr(e) if len(e) else None,
+                                    len(e)), "PolyaUrn::push")
+
+    def pop(self, m):
+        out = np.zeros((max(self.num_edges, 1), 2), np.uint32)
+        _check(lib().ans_polya_pop(m.h, self.num_nodes, self.loops, self.redraws, _np_ptr(out), self.num_edges),
+               "PolyaUrn::pop")
+        return Unordered((int(i), int(j)) for i, j in out[:self.num_edges])
+
+    def bits(self, x):  # src/graph_codec.rs:344-351
+        if not (self.loops and self.redraws):
+            return None
+        m = Message.zeros()
+        before = m.virtual_bits()
+        self.push(m, x)
+        return m.virtual_bits() - before
 
 
 # ============================================================== GPU bulk path (section 4)
@@ -1276,6 +1319,85 @@ class GpuTableSet:
         _check(lib().ans_dev_independent_decode(self.h, _dptr(d_tids), _dptr(d_in), _dptr(d_offsets), slot_cap,
                                                 _dptr(d_lens), n, chunk_len, gen_kind, seed, _dptr(d_syms), sym_bytes,
                                                 _dptr(d_status), _sptr(stream)), "ans_dev_independent_decode")
+
+
+class GpuPolyaUrn:
+    """PolyaUrn in bulk (include/ans_capi.h 5c): graph g's edges onto / from message g of a
+    container, one lane per graph, under the resume contract."""
+
+    def __init__(self, gpu, loops, redraws, directed=False):
+        if directed:
+            raise AnsError(ANS_E_ARG, "GpuPolyaUrn: directed graphs are not coded")
+        self.gpu, self.loops, self.redraws = gpu, int(bool(loops)), int(bool(redraws))
+
+    @staticmethod
+    def slack(max_nodes, max_edges):
+        """Bytes a message can grow by during a push or a pop (slot_cap of dev_push / dev_pop)."""
+        b = u64(0)
+        _check(lib().ans_gpu_polya_slack(max_nodes, max_edges, ctypes.byref(b)), "ans_gpu_polya_slack")
+        return b.value
+
+    @staticmethod
+    def _shapes(where, num_nodes, num_edges):
+        nn = np.ascontiguousarray(np.asarray(num_nodes, dtype=np.uint32))
+        ne = np.asarray(num_edges, dtype=np.uint64)
+        if nn.ndim != 1 or ne.shape != nn.shape:
+            raise AnsError(ANS_E_ARG, f"{where}: one node count and one edge count per graph")
+        eo = np.zeros(len(nn) + 1, np.uint64)
+        np.cumsum(ne, out=eo[1:])
+        return nn, eo
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        _check(fn(self.gpu.h, self.loops, self.redraws, num_graphs, *before, *after, _np_ptr(out), len(out),
+                  _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)), where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def push_graphs(self, num_nodes, edge_lists, data, offsets, lens):
+        """PolyaUrn::push of graph g's edges (edge_lists[g]: pairs) onto message g of the container
+        (data, offsets, lens), then flatten: returns the container of the results."""
+        where = "ans_gpu_polya_push_graphs"
+        lists = [_edge_pairs(e) for e in edge_lists]
+        nn, eo = self._shapes(where, num_nodes, [len(e) for e in lists])
+        edges = np.ascontiguousarray(np.concatenate(lists)) if int(eo[-1]) else np.zeros((1, 2), np.uint32)
+        g = len(nn)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        grow = self.slack(int(nn.max()) if g else 0, int(np.diff(eo).max()) if g else 0)
+        return self._call(where, lib().ans_gpu_polya_push_graphs, (_np_ptr(nn), _np_ptr(edges), _np_ptr(eo)),
+                          (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens)), g,
+                          data.size + g * grow)
+
+    def pop_graphs(self, num_nodes, num_edges, data, offsets, lens):
+        """PolyaUrn::pop of num_edges[g] edges from message g: returns (list of (E_g, 2) arrays,
+        container of what remains)."""
+        where = "ans_gpu_polya_pop_graphs"
+        nn, eo = self._shapes(where, num_nodes, num_edges)
+        g = len(nn)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        edges = np.zeros((max(int(eo[-1]), 1), 2), np.uint32)
+        grow = self.slack(int(nn.max()) if g else 0, int(np.diff(eo).max()) if g else 0)
+        container = self._call(
+            where, lib().ans_gpu_polya_pop_graphs, (_np_ptr(nn), _np_ptr(eo)),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(edges)), g,
+            data.size + g * grow)
+        return [edges[int(eo[k]):int(eo[k + 1])] for k in range(g)], container
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None):
+        """In place on device slots: d_lens is read and rewritten."""
+        _check(lib().ans_dev_polya_push(self.gpu.h, self.loops, self.redraws, num_graphs, _dptr(d_num_nodes),
+                                        _dptr(d_edges), _dptr(d_edge_offsets), max_nodes, max_edges, _dptr(d_slots),
+                                        slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_polya_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                d_lens, d_status, stream=None):
+        """... d_edges receives graph g's pairs at d_edge_offsets[g]."""
+        _check(lib().ans_dev_polya_pop(self.gpu.h, self.loops, self.redraws, num_graphs, _dptr(d_num_nodes),
+                                       _dptr(d_edges), _dptr(d_edge_offsets), max_nodes, max_edges, _dptr(d_slots),
+                                       slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_polya_pop")
 
 
 # ============================================================== graph models' bulk caller (section 5)

@@ -9,6 +9,7 @@
 #include <new>
 
 #include "ans_mset.hpp"
+#include "ans_polya.hpp"
 #include "ans_table.hpp"
 
 using namespace shuffle_coding;
@@ -293,6 +294,54 @@ int ans_mset_pop(ans_msg* m, const ans_table* t, uint32_t* out, size_t n) {
             msg.renorm(p * (MAX_MIN_HEAD / norm));
             msg.head = norm * (msg.head / p) + c + msg.head % p;
         }
+    });
+}
+
+// ---- the Pólya urn edge-index codec on one message (ans_polya.hpp): multiset_shuffle_codec(
+// PolyaUrnEdgeIndicesCodec<Undirected>), src/graph_codec.rs:210-375
+extern "C++" {
+namespace {
+struct VecWs {  // the state's arrays, one after the other in a vector
+    uint32_t* p;
+    VecAcc at(uint64_t o) const { return VecAcc{p + o}; }
+};
+struct HostMsg {  // a Message as polya::Coder takes it
+    Message& msg;
+    uint64_t& head;
+    bool renorm(uint64_t min_head) {
+        try {
+            msg.renorm(min_head);
+            return true;
+        } catch (const AnsError&) {  // the Empty generator, src/ans.rs:144
+            return false;
+        }
+    }
+};
+template <class F>
+int polya_host(ans_msg* m, uint32_t num_nodes, size_t num_edges, F&& f) {
+    return guarded([&] {
+        if (num_edges > polya::kMaxEdges) throw AnsError(ANS_E_ARG, "2^31 or more edges");
+        std::vector<uint32_t> ws(polya::ws_entries(num_nodes, num_edges));
+        auto st = polya::State<VecAcc>::make(VecWs{ws.data()}, num_nodes, num_edges);
+        HostMsg hm{m->m, m->m.head};
+        polya::Coder<HostMsg> c{hm, ANS_OK};
+        if (const int rc = f(c, st)) throw AnsError(rc, ans_status_string(rc));
+    });
+}
+}  // namespace
+}  // extern "C++" (templates)
+
+int ans_polya_push(ans_msg* m, uint32_t num_nodes, int loops, int redraws, const uint32_t* edges, size_t num_edges) {
+    if (!m || (num_edges && !edges)) return ANS_E_ARG;
+    return polya_host(m, num_nodes, num_edges, [&](auto& c, auto& st) {
+        return polya::push_graph(c, st, num_nodes, loops != 0, redraws != 0, edges, static_cast<uint32_t>(num_edges));
+    });
+}
+
+int ans_polya_pop(ans_msg* m, uint32_t num_nodes, int loops, int redraws, uint32_t* edges, size_t num_edges) {
+    if (!m || (num_edges && !edges)) return ANS_E_ARG;
+    return polya_host(m, num_nodes, num_edges, [&](auto& c, auto& st) {
+        return polya::pop_graph(c, st, num_nodes, loops != 0, redraws != 0, edges, static_cast<uint32_t>(num_edges));
     });
 }
 

@@ -134,4 +134,30 @@ inline int download_container(ans_gpu* g, const uint8_t* d_slots, uint64_t slot_
     return ANS_OK;
 }
 
+// The resume head of the host-buffer push / pop entries of ans_mset.hip and ans_polya.hip: the
+// dense container in, expanded into slots of the longest stream + grow bytes (rounded to 128) on
+// the context's stream, with the chunk table, a zeroed status block and, when given, the nchunks + 1
+// chunk starts.
+struct Stage {
+    DevStreams d;
+    DevBuf slots, starts;
+    uint64_t cap = 0;
+};
+inline int stage_in(ans_gpu* g, const uint64_t* starts, uint64_t nchunks, const uint8_t* in, uint64_t in_len,
+                    const uint64_t* in_offsets, const uint64_t* in_lens, uint64_t grow, Stage& st) {
+    std::vector<uint32_t> l32;
+    uint64_t lmax = 0;
+    int rc = narrow_lens(in_offsets, in_lens, nchunks, in_len, l32, &lmax);
+    if (rc) return rc;
+    st.cap = (lmax + grow + 127) & ~uint64_t(127);
+    const hipStream_t s = g->stream;
+    if ((rc = upload_streams(in, in_len, in_offsets, l32, s, st.d))) return rc;
+    ANS_HIP_TRY(st.slots.alloc(nchunks * st.cap));
+    if (starts) {
+        ANS_HIP_TRY(st.starts.alloc(8 * (nchunks + 1)));
+        ANS_HIP_TRY(hipMemcpyAsync(st.starts.p, starts, 8 * (nchunks + 1), hipMemcpyHostToDevice, s));
+    }
+    return ans_dev_expand(g, st.d.in.as<uint8_t>(), st.d.offs.as<uint64_t>(), st.d.lens.as<uint32_t>(), nchunks,
+                          st.slots.as<uint8_t>(), st.cap, s);
+}
 }  // namespace

@@ -705,6 +705,8 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
         case kRecPop64: w = std::snprintf(o, room - 1, "k_pop64<%s>", sym); break;
         case kRecMsetPush: w = std::snprintf(o, room - 1, "k_mset_push<%s,cnt=%s>", sym, a[0] ? "lds" : "global"); break;
         case kRecMsetPop: w = std::snprintf(o, room - 1, "k_mset_pop<%s,cnt=%s>", sym, a[0] ? "lds" : "global"); break;
+        case kRecPolyaPush: w = std::snprintf(o, room - 1, "k_polya_push<redraws=%d>", a[0]); break;
+        case kRecPolyaPop: w = std::snprintf(o, room - 1, "k_polya_pop<redraws=%d>", a[0]); break;
         default: w = std::snprintf(o, room - 1, "?"); break;
         }
         at += static_cast<size_t>(w);

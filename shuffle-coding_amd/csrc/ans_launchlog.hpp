@@ -26,6 +26,8 @@ enum LaunchKind : uint8_t {
     kRecPop64,
     kRecMsetPush,       // k_mset_push / k_mset_pop (ans_mset.hip)  a = {counts in LDS (1) or global memory (0)}
     kRecMsetPop,
+    kRecPolyaPush,      // k_polya_push / k_polya_pop (ans_polya.hip)  a = {kRedraws}
+    kRecPolyaPop,
 };
 struct LaunchRec {
     uint8_t kind;

@@ -366,29 +366,8 @@ int dev_mset_pop(ans_gpu_tableset* ts, uint32_t table, uint8_t* d_slots, uint64_
 
 // ---- host buffers in and out, synchronous (as ans_gpu_independent_push_chunks / _pop_chunks): the
 // dense container in is expanded into slots with room for each result, the chunks are coded in
-// place and the slots are packed into the container out.  starts == NULL: fixed chunks.
-struct Stage {
-    DevStreams d;
-    DevBuf slots, starts;
-    uint64_t cap = 0;
-};
-int stage_in(ans_gpu* g, const uint64_t* starts, uint64_t nchunks, const uint8_t* in, uint64_t in_len,
-             const uint64_t* in_offsets, const uint64_t* in_lens, uint64_t grow, Stage& st) {
-    std::vector<uint32_t> l32;
-    uint64_t lmax = 0;
-    int rc = narrow_lens(in_offsets, in_lens, nchunks, in_len, l32, &lmax);
-    if (rc) return rc;
-    st.cap = (lmax + grow + 127) & ~uint64_t(127);
-    const hipStream_t s = g->stream;
-    if ((rc = upload_streams(in, in_len, in_offsets, l32, s, st.d))) return rc;
-    HIP_TRY(st.slots.alloc(nchunks * st.cap));
-    if (starts) {
-        HIP_TRY(st.starts.alloc(8 * (nchunks + 1)));
-        HIP_TRY(hipMemcpyAsync(st.starts.p, starts, 8 * (nchunks + 1), hipMemcpyHostToDevice, s));
-    }
-    return ans_dev_expand(g, st.d.in.as<uint8_t>(), st.d.offs.as<uint64_t>(), st.d.lens.as<uint32_t>(), nchunks,
-                          st.slots.as<uint8_t>(), st.cap, s);
-}
+// place and the slots are packed into the container out (Stage, stage_in: ans_hostio.hpp).
+// starts == NULL: fixed chunks.
 uint64_t longest_of(const uint64_t* starts, uint64_t nchunks, uint64_t chunk_len) {
     uint64_t longest = chunk_len;
     if (starts)
