@@ -212,6 +212,13 @@ int ans_gpu_table_paths(const ans_gpu_table *gt, uint32_t *paths);
  * NUL-terminated text into buf; a shorter buf (or buf == NULL) is ANS_E_LEN with *len set.
  * For tests and tuning: the text is not a stable interface. */
 int ans_gpu_last_launch(const ans_gpu *g, char *buf, size_t cap, size_t *len);
+/* The workgroup count of launch `index` (0-based, in launch order) of the same record.  Kept for
+ * the kernels whose lanes are bounded by a workspace of the context's, where one lane codes several
+ * items in turn: k_mset_push / k_mset_pop (saturating at 32,767: the cnt=lds form launches one
+ * lane per chunk) and k_polya_push / k_polya_pop; *workgroups = 0 for the other kernels, whose
+ * records do not keep it.  Lanes = 64 x workgroups.  ANS_E_ARG for an index at or past the
+ * launches recorded.  For tests and tuning, as the text is. */
+int ans_gpu_last_launch_grid(const ans_gpu *g, uint32_t index, uint32_t *workgroups);
 /* worst-case stream bytes of one chunk of chunk_len symbols, rounded up to 16 */
 int ans_gpu_slot_capacity(const ans_gpu_table *gt, uint64_t chunk_len, uint64_t *slot_cap);
 

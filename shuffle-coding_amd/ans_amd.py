@@ -77,6 +77,7 @@ SIGNATURES = {
     "ans_gpu_set_batch_bytes": (ci, [vp, u64]),
     "ans_gpu_pipe_depth": (ci, [vp, ctypes.POINTER(ci)]),
     "ans_gpu_last_launch": (ci, [vp, ctypes.c_char_p, sz, ctypes.POINTER(sz)]),
+    "ans_gpu_last_launch_grid": (ci, [vp, ctypes.c_uint32, u32p]),
     "ans_host_alloc": (ci, [sz, ctypes.POINTER(vp)]),
     "ans_host_free": (None, [vp]),
     "ans_gpu_table_create": (ci, [vp, vp, ctypes.POINTER(vp)]),
@@ -732,6 +733,13 @@ class Gpu:
         buf = ctypes.create_string_buffer(n.value + 1)
         _check(lib().ans_gpu_last_launch(self.h, buf, n.value + 1, ctypes.byref(n)), "ans_gpu_last_launch")
         return buf.value.decode("ascii")
+
+    def last_launch_grid(self, index=0):
+        """The workgroups of launch `index` of that record (ans_gpu_last_launch_grid): kept by the
+        multiset and Pólya urn kernels, 0 for the others; lanes = 64 x workgroups."""
+        wg = ctypes.c_uint32(0)
+        _check(lib().ans_gpu_last_launch_grid(self.h, index, ctypes.byref(wg)), "ans_gpu_last_launch_grid")
+        return wg.value
 
     def status(self, d_status, stream=None):
         st = ci(0)

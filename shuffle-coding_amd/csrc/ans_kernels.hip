@@ -719,6 +719,18 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
     return ANS_OK;
 } ANS_CATCH
 
+// The workgroup count of a recorded launch (include/ans_capi.h): kept by the kinds whose launch
+// bounds the lanes by a workspace, 0 for the others.
+int ans_gpu_last_launch_grid(const ans_gpu* g, uint32_t index, uint32_t* workgroups) try {
+    if (!g || !workgroups) return ANS_E_ARG;
+    const LaunchLog& log = g->last;
+    if (index >= std::min(log.n, LaunchLog::kCap)) return ANS_E_ARG;
+    const LaunchRec& r = log.r[index];
+    const int slot = rec_grid_slot(r.kind);
+    *workgroups = slot < 0 ? 0u : static_cast<uint32_t>(r.a[slot]);
+    return ANS_OK;
+} ANS_CATCH
+
 void ans_gpu_free(ans_gpu* g) try {
     if (!g) return;
     (void)hipSetDevice(g->device);

@@ -24,9 +24,9 @@ enum LaunchKind : uint8_t {
     kRecDecode64,
     kRecPush64,
     kRecPop64,
-    kRecMsetPush,       // k_mset_push / k_mset_pop (ans_mset.hip)  a = {counts in LDS (1) or global memory (0)}
+    kRecMsetPush,       // k_mset_push / k_mset_pop (ans_mset.hip)  a = {counts in LDS (1) or global memory (0), workgroups}
     kRecMsetPop,
-    kRecPolyaPush,      // k_polya_push / k_polya_pop (ans_polya.hip)  a = {kRedraws}
+    kRecPolyaPush,      // k_polya_push / k_polya_pop (ans_polya.hip)  a = {kRedraws, workgroups}
     kRecPolyaPop,
 };
 struct LaunchRec {
@@ -34,6 +34,14 @@ struct LaunchRec {
     uint8_t sym_bytes;
     int16_t a[6];
 };
+// The slot of a[] in which a record kind keeps its launch's workgroup count (ans_gpu_last_launch_grid
+// reads it; the text of ans_gpu_last_launch does not show it), or -1 for a kind that keeps none.
+constexpr int rec_grid_slot(uint8_t kind) {
+    return kind == kRecMsetPush || kind == kRecMsetPop || kind == kRecPolyaPush || kind == kRecPolyaPop ? 1 : -1;
+}
+// ... and the count as the slot holds it: the workspace forms launch at most 8 workgroups per CU;
+// the LDS form of the multiset kernels, one lane per chunk, can pass an int16_t and saturates.
+constexpr int rec_grid(uint64_t workgroups) { return workgroups > 32767 ? 32767 : static_cast<int>(workgroups); }
 struct LaunchLog {
     static constexpr uint32_t kCap = 8;  // (a call starts at most three coder kernels)
     uint32_t n = 0;                      // launches since the clear (entries past kCap are counted only)

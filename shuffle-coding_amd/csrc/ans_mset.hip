@@ -328,7 +328,7 @@ int dev_mset_push(ans_gpu_tableset* ts, uint32_t table, const void* d_syms, int 
     log.clear();
     with_sym_type(w, [&](auto t) {
         using Sym = decltype(t);
-        log.add(kRecMsetPush, sizeof(Sym), pl.lds);
+        log.add(kRecMsetPush, sizeof(Sym), pl.lds, rec_grid(pl.grid));
         if (pl.lds)
             k_mset_push<Sym, LdsCnt><<<pl.grid, kThreads, pl.lds_bytes, s>>>(
                 pl.md, pl.mt, static_cast<const Sym*>(d_syms), d_starts, n, chunk_len, nchunks, d_slots, slot_cap, d_lens,
@@ -350,7 +350,7 @@ int dev_mset_pop(ans_gpu_tableset* ts, uint32_t table, uint8_t* d_slots, uint64_
     log.clear();
     with_sym_type(w, [&](auto t) {
         using Sym = decltype(t);
-        log.add(kRecMsetPop, sizeof(Sym), pl.lds);
+        log.add(kRecMsetPop, sizeof(Sym), pl.lds, rec_grid(pl.grid));
         if (pl.lds)
             k_mset_pop<Sym, LdsCnt><<<pl.grid, kThreads, pl.lds_bytes, s>>>(
                 pl.md, pl.mt, d_slots, slot_cap, d_lens, d_starts, n, chunk_len, nchunks, static_cast<Sym*>(d_syms),

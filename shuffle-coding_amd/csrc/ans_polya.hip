@@ -190,7 +190,7 @@ int dev_polya(bool push, ans_gpu* g, int loops, int redraws, uint64_t num_graphs
     const PolyaArgs a{num_graphs, d_num_nodes, d_edge_offsets, max_nodes, max_edges, d_slots,
                       slot_cap,   d_lens,      d_status,       ws,        loops};
     g->last.clear();
-    g->last.add(push ? kRecPolyaPush : kRecPolyaPop, 0, redraws != 0);
+    g->last.add(push ? kRecPolyaPush : kRecPolyaPop, 0, redraws != 0, rec_grid(grid));
     if (push) {
         if (redraws) k_polya_push<true><<<grid, kThreads, 0, s>>>(a, d_edges);
         else k_polya_push<false><<<grid, kThreads, 0, s>>>(a, d_edges);

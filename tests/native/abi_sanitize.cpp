@@ -2,12 +2,16 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer: random operation sequences on the library's
 // Message / Categorical / Uniform / two-phase / IID entry points, each mirrored on the C oracle
 // (oracle/ans_oracle.c, test infrastructure) and compared head by head and byte by byte, plus
-// the error paths the reference panics on.  Built and run by tests/test_native_sanitize.py with
+// the error paths the reference panics on; then the multiset and Pólya urn codecs on one message
+// (ans_mset_push / _pop, ans_polya_push / _pop): round trips across their paths, and pops of bytes
+// no push wrote, each a listed status or a result inside the alphabet.  Built and run by tests/test_native_sanitize.py with
 // host code only (ans_capi.cpp + the oracle; no HIP), so it runs without a GPU.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <utility>
 #include <vector>
 
 #include "../../include/ans_capi.h"
@@ -49,6 +53,127 @@ static std::vector<uint8_t> flat(const orc_msg* m) {
     std::vector<uint8_t> b(orc_msg_flatten(m, nullptr, 0));
     orc_msg_flatten(m, b.data(), b.size());
     return b;
+}
+
+// ---- the multiset and Pólya urn codecs on one message (include/ans_capi.h after section 3): the
+// sanitizers see the exactly sized workspaces ans_capi.cpp allocates per call
+static std::vector<uint8_t> random_bytes(std::mt19937_64& rng, size_t n, bool top_nonzero) {
+    std::vector<uint8_t> b(n);
+    for (auto& v : b) v = static_cast<uint8_t>(rng());
+    if (top_nonzero && n) b.back() |= 1;  // such a seed comes back byte for byte
+    return b;
+}
+static ans_msg* unflatten_empty(const std::vector<uint8_t>& b) {
+    ans_msg* m = nullptr;
+    CHECK(ans_msg_unflatten(b.data(), b.size(), ANS_GEN_EMPTY, 0, &m) == ANS_OK);
+    return m;
+}
+static ans_table* random_table(std::mt19937_64& rng, uint32_t nsym) {
+    std::vector<uint64_t> masses(nsym);
+    for (auto& v : masses) v = 1 + rng() % 4095;
+    ans_table* t = nullptr;
+    CHECK(ans_table_create(masses.data(), nsym, &t) == ANS_OK);
+    return t;
+}
+
+// push n values onto a seed, pop them from what the push left: the same multiset, the same seed
+static void mset_roundtrip(std::mt19937_64& rng, const ans_table* t, uint32_t nsym, size_t n) {
+    std::vector<uint32_t> syms(n), back(n, 0xDEADBEEFu);
+    for (auto& s : syms) s = static_cast<uint32_t>(rng() % nsym);
+    const std::vector<uint8_t> seed = random_bytes(rng, 512, true);
+    ans_msg* m = unflatten_empty(seed);
+    CHECK(ans_mset_push(m, t, syms.data(), n) == ANS_OK);
+    const std::vector<uint8_t> pushed = flat(m);
+    ans_msg_free(m);
+    m = unflatten_empty(pushed);
+    CHECK(ans_mset_pop(m, t, back.data(), n) == ANS_OK);
+    std::sort(syms.begin(), syms.end());
+    std::sort(back.begin(), back.end());
+    CHECK(back == syms);
+    std::vector<uint8_t> want = seed;
+    if (n == 0) want.insert(want.end(), 2, 0);  // each call is flatten(unflatten(B)) = B ++ [0]
+    CHECK(flat(m) == want);
+    ans_msg_free(m);
+}
+
+static void polya_roundtrip(std::mt19937_64& rng, uint32_t n, size_t E, bool loops, bool redraws) {
+    std::vector<std::pair<uint32_t, uint32_t>> all;
+    for (uint32_t j = 0; j < n; ++j)
+        for (uint32_t i = 0; i < (loops ? j + 1 : j); ++i) all.emplace_back(i, j);
+    CHECK(E <= all.size());
+    std::shuffle(all.begin(), all.end(), rng);
+    all.resize(E);
+    std::vector<uint32_t> e, back(2 * E, 0xDEADBEEFu);
+    for (const auto& p : all) {
+        e.push_back(p.first);
+        e.push_back(p.second);
+    }
+    const std::vector<uint8_t> seed = random_bytes(rng, 256, true);
+    ans_msg* m = unflatten_empty(seed);
+    CHECK(ans_polya_push(m, n, loops, redraws, e.data(), E) == ANS_OK);
+    const std::vector<uint8_t> pushed = flat(m);
+    ans_msg_free(m);
+    m = unflatten_empty(pushed);
+    CHECK(ans_polya_pop(m, n, loops, redraws, back.data(), E) == ANS_OK);
+    std::vector<std::pair<uint32_t, uint32_t>> got;
+    for (size_t k = 0; k < E; ++k) got.emplace_back(back[2 * k], back[2 * k + 1]);
+    std::sort(all.begin(), all.end());
+    std::sort(got.begin(), got.end());
+    CHECK(got == all);
+    std::vector<uint8_t> want = seed;
+    if (E == 0) want.insert(want.end(), 2, 0);
+    CHECK(flat(m) == want);
+    ans_msg_free(m);
+}
+
+static void mset_and_polya(std::mt19937_64& rng) {
+    ans_table* t256 = random_table(rng, 256);
+    ans_table* t1030 = random_table(rng, 1030);
+    mset_roundtrip(rng, t256, 256, 200);
+    mset_roundtrip(rng, t1030, 1030, 96);
+    mset_roundtrip(rng, t256, 256, 0);
+    mset_roundtrip(rng, t256, 256, 1);
+    {  // a one-byte seed cannot pay for the first orbit pop and table push
+        std::vector<uint32_t> syms(64);
+        for (auto& s : syms) s = static_cast<uint32_t>(rng() % 256);
+        ans_msg* m = unflatten_empty({0x07});
+        CHECK(ans_mset_push(m, t256, syms.data(), syms.size()) == ANS_E_EXHAUSTED);
+        ans_msg_free(m);
+    }
+    for (size_t E : {size_t(0), size_t(11), size_t(12), size_t(90)})
+        for (int setting = 0; setting < 4; ++setting) polya_roundtrip(rng, 40, E, setting & 1, setting & 2);
+    // bytes no push wrote: a listed status, or values / pairs of the alphabet
+    int mset_ok = 0, mset_status = 0, polya_ok = 0, polya_status = 0;
+    for (int k = 0; k < 200; ++k) {
+        const bool wide = k & 1;
+        const uint32_t nsym = wide ? 1030 : 256;
+        const size_t n = rng() % 201;
+        std::vector<uint32_t> out(n, 0xDEADBEEFu);
+        ans_msg* m = unflatten_empty(random_bytes(rng, 1 + rng() % 300, false));
+        const int rc = ans_mset_pop(m, wide ? t1030 : t256, out.data(), n);
+        CHECK(rc == ANS_OK || rc == ANS_E_EXHAUSTED);
+        if (rc == ANS_OK)
+            for (uint32_t v : out) CHECK(v < nsym);
+        ++(rc == ANS_OK ? mset_ok : mset_status);
+        ans_msg_free(m);
+    }
+    for (int k = 0; k < 200; ++k) {
+        const bool loops = k & 1, redraws = k & 2;
+        const uint32_t n = 1 + static_cast<uint32_t>(rng() % 40);
+        const size_t E = rng() % 121;
+        std::vector<uint32_t> out(2 * E, 0xDEADBEEFu);
+        ans_msg* m = unflatten_empty(random_bytes(rng, 1 + rng() % 300, false));
+        const int rc = ans_polya_pop(m, n, loops, redraws, out.data(), E);
+        CHECK(rc == ANS_OK || rc == ANS_E_EXHAUSTED || rc == ANS_E_ZERO_MASS || rc == ANS_E_SYMBOL || rc == ANS_E_ARG);
+        if (rc == ANS_OK)
+            for (size_t p = 0; p < E; ++p)
+                CHECK(out[2 * p] <= out[2 * p + 1] && out[2 * p + 1] < n && (loops || out[2 * p] != out[2 * p + 1]));
+        ++(rc == ANS_OK ? polya_ok : polya_status);
+        ans_msg_free(m);
+    }
+    CHECK(mset_ok > 0 && mset_status > 0 && polya_ok > 0 && polya_status > 0);  // (the inputs reach both ends)
+    ans_table_free(t256);
+    ans_table_free(t1030);
 }
 
 int main() {
@@ -162,6 +287,7 @@ int main() {
     ans_msg_free(m);
     for (auto* h : lt) ans_table_free(h);
     for (auto* h : ot) orc_cat_free(h);
+    mset_and_polya(rng);
     if (failures) return 1;
     std::printf("abi_sanitize ok\n");
     return 0;
