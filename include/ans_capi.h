@@ -145,6 +145,46 @@ int ans_mset_pop(ans_msg *m, const ans_table *t, uint32_t *out, size_t n);
  * coded (the reference asserts !is_directed, :220). */
 int ans_polya_push(ans_msg *m, uint32_t num_nodes, int loops, int redraws, const uint32_t *edges, size_t num_edges);
 int ans_polya_pop(ans_msg *m, uint32_t num_nodes, int loops, int redraws, uint32_t *edges, size_t num_edges);
+/* One undirected, unlabelled graph under the autoregressive Erdős–Rényi model, as a labelled graph
+ * or up to the order of its nodes: Autoregressive(ErdosRenyiSliceCodecs) (src/recursive/mod.rs:190-216,
+ * src/recursive/graph/slice.rs:16-59; the harness's ord_AE) and ShuffleCodec<ErdosRenyiSliceCodecs,
+ * WLOrbitCodecs<GraphPrefix>> with wl_iter = 0 (src/recursive/mod.rs:117-148, src/recursive/graph/
+ * incomplete.rs:189-236; the harness's wl0r_AE with the extra half iteration, wl0-r_AE without).
+ * edges: num_edges distinct uint32 pairs (i, j) with i <= j < num_nodes, fewer than 2^31 of them, in
+ * any order.  bern: a table of exactly two symbols, [norm - mass, mass] (ans_table_create_bernoulli);
+ * symbol 1 says "the pair is an edge".  The slice of position v is the 0/1 vector over (v, v+1) ..
+ * (v, num_nodes-1), then (v, v) when `loops`, coded as IID<Bernoulli>: pushed last entry first.
+ *   orbits = ANS_ORBITS_NONE:      push codes slice num_nodes-1 .. 0, pop decodes slice 0 .. num_nodes-1;
+ *                                  the decoded graph is the input.
+ *   orbits = ANS_ORBITS_DEGREE:    the class of a known node is its degree in the whole graph (a loop
+ *                                  counts once), classes in ascending order of their id, SipHash-1-3
+ *                                  (keys 0, 0) over the 16 bytes (ans_orbit_id(0), degree).
+ *                                  push: for L = num_nodes .. 1 a class is POPPED under the counts of
+ *                                  the classes at positions < L (norm L), its smallest position and
+ *                                  position L - 1 change nodes, and slice L - 1 is pushed.
+ *                                  pop: for v = 0 .. num_nodes-1 slice v is popped and the class of
+ *                                  position v is PUSHED under the counts of positions <= v.
+ *                                  The decoded graph is the input relabelled by the permutation the
+ *                                  push chose.  Saves log2(n! / prod c_k!) bits, c_k the number of
+ *                                  nodes of the k-th distinct degree.
+ *   orbits = ANS_ORBITS_ONE_CLASS: the same with every known node in one class (saves nothing).
+ * push: perm is NULL or receives num_nodes entries, perm[position] = the input node there (the
+ * identity for NONE).  pop: edges receives the pairs (v, w), v <= w, as positions, in pop order (v
+ * ascending, within v the slice's order, the loop last), *num_edges their number; more than cap
+ * of them is ANS_E_LEN.
+ * ANS_E_SYMBOL: i > j, a node >= num_nodes, a loop without `loops`, a pair given twice.
+ * ANS_E_ZERO_MASS: a needed symbol of mass 0, as ans_cat_push.  ANS_E_EXHAUSTED: as ans_cat_pop.
+ * ANS_E_ARG: a table without exactly two symbols, an `orbits` outside the three values, 2^31 or
+ * more pairs or nodes, or two degrees <= num_nodes with one class id (none below 70,000).
+ * A failed call leaves the message wherever the failing step found it.  Deeper WL iterations,
+ * PolyaUrnSliceCodecs, labels and directed graphs are not coded. */
+#define ANS_ORBITS_NONE 0
+#define ANS_ORBITS_ONE_CLASS 1
+#define ANS_ORBITS_DEGREE 2
+int ans_ar_er_push(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int orbits,
+                   const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
+int ans_ar_er_pop(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int orbits, uint32_t *edges,
+                  size_t cap, size_t *num_edges);
 
 /* ======================================================================
  * (4) GPU bulk path (MI355X / gfx950) — the data-parallel hot path.
@@ -203,9 +243,10 @@ int ans_gpu_table_paths(const ans_gpu_table *gt, uint32_t *paths);
  *   k_encode64<catset,u8>   k_decode64<catset,u8>   k_push64<u8>   k_pop64<u8>
  *   k_mset_push<u8,cnt=lds>   k_mset_pop<u16,cnt=global>      (cnt: where the per-lane counts live)
  *   k_polya_push<redraws=0>   k_polya_pop<redraws=1>          (section 5c)
+ *   k_arer_push<orbits=2>   k_arer_pop<orbits=0>              (section 5d)
  * The calls that write it are the Categorical table's (sections 3 and 4: fixed, ragged and variable
  * chunks, host or device buffers; a pipelined host call leaves its last batch's launches), the
- * Independent ones (new messages and resume), the multiset ones and the Pólya urn ones; helper kernels (staging, compaction) are not named,
+ * Independent ones (new messages and resume), the multiset ones, the Pólya urn ones and the autoregressive Erdős–Rényi ones; helper kernels (staging, compaction) are not named,
  * and the other calls (and calls that return before any launch: no symbols, bad arguments) leave
  * the record as it was.  Empty before the first such call.
  * Writes *len = the text's bytes (without the terminating NUL) and, if cap > *len, the
@@ -215,7 +256,7 @@ int ans_gpu_last_launch(const ans_gpu *g, char *buf, size_t cap, size_t *len);
 /* The workgroup count of launch `index` (0-based, in launch order) of the same record.  Kept for
  * the kernels whose lanes are bounded by a workspace of the context's, where one lane codes several
  * items in turn: k_mset_push / k_mset_pop (saturating at 32,767: the cnt=lds form launches one
- * lane per chunk) and k_polya_push / k_polya_pop; *workgroups = 0 for the other kernels, whose
+ * lane per chunk), k_polya_push / k_polya_pop and k_arer_push / k_arer_pop; *workgroups = 0 for the other kernels, whose
  * records do not keep it.  Lanes = 64 x workgroups.  ANS_E_ARG for an index at or past the
  * launches recorded.  For tests and tuning, as the text is. */
 int ans_gpu_last_launch_grid(const ans_gpu *g, uint32_t index, uint32_t *workgroups);
@@ -705,6 +746,58 @@ int ans_gpu_polya_pop_graphs(ans_gpu *g, int loops, int redraws, uint64_t num_gr
                              const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
                              const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges, uint8_t *out,
                              uint64_t out_cap, uint64_t *offsets, uint64_t *lens, uint64_t *total);
+
+/* ======================================================================
+ * (5d) The autoregressive Erdős–Rényi graph codecs in bulk: ans_ar_er_push / ans_ar_er_pop
+ *      (section 3) of graph g onto / from the message ALREADY in slot g, one lane per graph, under
+ *      the resume contract of section 4b as section 5c has it: the input is Message::unflatten(slot
+ *      bytes, d_lens[g]) with the Empty tail, the result is flattened back into the slot and
+ *      d_lens[g] is its length.  The bytes equal the host codec's.  gt is the Bernoulli (two symbols,
+ *      else ANS_E_ARG; any norm a table takes).
+ *      push: graph g has d_num_nodes[g] nodes and the pairs [d_edge_offsets[g], d_edge_offsets[g+1])
+ *      of d_edges (num_graphs + 1 offsets); d_perm is NULL or holds num_graphs * max_nodes entries,
+ *      graph g's permutation at d_perm + g * max_nodes.
+ *      pop: the offsets are CAPACITIES: graph g's pairs are written from d_edge_offsets[g] on, at most
+ *      d_edge_offsets[g+1] - d_edge_offsets[g] of them, and d_num_edges[g] is their number.
+ *      Statuses are OR-ed into *d_status with d_lens[g] = 0 (and d_num_edges[g] = 0) for that graph
+ *      alone: those of ans_ar_er_push / _pop; ANS_E_ARG for a graph of more than max_nodes nodes or
+ *      (push) max_edges pairs; ANS_E_LEN for a result past slot_cap, a d_lens[g] above it, or more
+ *      pairs than the graph's capacity.  With slot_cap >= d_lens[g] + ans_gpu_ar_er_slack(gt,
+ *      max_nodes, loops) neither call meets ANS_E_LEN for a slot: with s = max_nodes (max_nodes - 1)
+ *      / 2 + max_nodes * loops indicators, pmin the smaller nonzero mass, the slack is
+ *      max(s * (bitlen(norm / pmin) + (norm > 2^36)), max_nodes * bitlen(max_nodes)) / 8 + 1
+ *      + (s + max_nodes) / 2^20 + 16 bytes.  The host-buffer calls apply it.
+ *      The per-lane state (push: 6 max_nodes + 2 max_edges + 2 dwords, pop: 2 max_nodes + 1) lives in
+ *      the workspace of sections 4b / 5c, under the same rule: calls on one context must not share
+ *      it between streams running at the same time; it is sized by the lanes resident, at most
+ *      256 MiB, and bounds whose single wave passes that are ANS_E_ARG before anything is launched,
+ *      as are max_edges >= 2^31.  The degrees' class ranks are a table of max_nodes + 1 entries the
+ *      context keeps; a call with another max_nodes rebuilds it, which waits for the device.
+ *      Kernel names in ans_gpu_last_launch: k_arer_push<orbits=2>, k_arer_pop<orbits=0>, their
+ *      workgroups in ans_gpu_last_launch_grid.
+ * ====================================================================== */
+int ans_gpu_ar_er_slack(const ans_gpu_table *gt, uint32_t max_nodes, int loops, uint64_t *bytes);
+int ans_dev_ar_er_push(ans_gpu_table *gt, int loops, int orbits, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                       const uint32_t *d_edges, const uint64_t *d_edge_offsets, uint32_t max_nodes,
+                       uint64_t max_edges, uint32_t *d_perm /* NULL or num_graphs * max_nodes */, uint8_t *d_slots,
+                       uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_ar_er_pop(ans_gpu_table *gt, int loops, int orbits, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                      uint32_t *d_edges /* out */, const uint64_t *d_edge_offsets /* capacities */,
+                      uint32_t *d_num_edges /* out */, uint32_t max_nodes, uint8_t *d_slots /* in/out */,
+                      uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, a dense container in and one out exactly as
+ * ans_gpu_polya_push_graphs / _pop_graphs (out == NULL is the size query; pop still fills out_edges
+ * and out_num_edges).  perm is NULL or holds num_graphs * (the largest num_nodes) entries, graph g's
+ * at perm + g * that.  pop: edge_offsets are capacities as above, out_num_edges[g] the pairs of graph g. */
+int ans_gpu_ar_er_push_graphs(ans_gpu_table *gt, int loops, int orbits, uint64_t num_graphs, const uint32_t *num_nodes,
+                              const uint32_t *edges, const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                              const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *perm, uint8_t *out,
+                              uint64_t out_cap, uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_ar_er_pop_graphs(ans_gpu_table *gt, int loops, int orbits, uint64_t num_graphs, const uint32_t *num_nodes,
+                             const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                             const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges,
+                             uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
+                             uint64_t *lens, uint64_t *total);
 
 #ifdef __cplusplus
 }

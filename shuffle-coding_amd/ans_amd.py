@@ -26,6 +26,7 @@ LIB_PATH = os.environ.get("SHUFFLE_CODING_AMD_LIB") or os.path.join(HERE, "lib",
 ANS_OK, ANS_E_ZERO_MASS, ANS_E_EXHAUSTED, ANS_E_LEN, ANS_E_SYMBOL = 0, 1, 2, 3, 4
 ANS_E_NORM_RANGE, ANS_E_DEVICE, ANS_E_ALLOC, ANS_E_ARG, ANS_E_MISMATCH = 5, 6, 7, 8, 9
 GEN_ZEROS, GEN_EMPTY, GEN_RANDOM = 0, 1, 2
+ORBITS_NONE, ORBITS_ONE_CLASS, ORBITS_DEGREE = 0, 1, 2
 ANS_PATH_ENC_LDS, ANS_PATH_ENC_GLOBAL, ANS_PATH_DEC_LDS, ANS_PATH_DEC_GLOBAL = 1, 2, 4, 8
 ANS_PATH_ENC_WIDE, ANS_PATH_DEC_WIDE = 16, 32
 ANS_PATH_DEC_COMPACT = 64
@@ -158,6 +159,13 @@ SIGNATURES = {
     "ans_dev_polya_pop": (ci, [vp, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
     "ans_gpu_polya_push_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_polya_pop_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_ar_er_push": (ci, [vp, vp, ctypes.c_uint32, ci, ci, vp, sz, vp]),
+    "ans_ar_er_pop": (ci, [vp, vp, ctypes.c_uint32, ci, ci, vp, sz, ctypes.POINTER(sz)]),
+    "ans_gpu_ar_er_slack": (ci, [vp, ctypes.c_uint32, ci, u64p]),
+    "ans_dev_ar_er_push": (ci, [vp, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_er_pop": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, vp, u64, vp, vp, vp]),
+    "ans_gpu_ar_er_push_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_er_pop_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
     "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
     "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
@@ -691,6 +699,42 @@ class PolyaUrn(Codec):
         return m.virtual_bits() - before
 
 
+def _two_symbol_table(bernoulli):
+    """The Categorical behind a Bernoulli (or a Categorical given as one: the library checks it)."""
+    return getattr(bernoulli, "categorical", bernoulli)
+
+
+class AutoregressiveER(Codec):
+    """An undirected, unlabelled graph under the autoregressive Erdős–Rényi model, on the host through
+    ans_ar_er_push / ans_ar_er_pop: Autoregressive(ErdosRenyiSliceCodecs) for orbits = ORBITS_NONE
+    (src/recursive/mod.rs:190-216, src/recursive/graph/slice.rs:16-59), else recursive shuffle coding
+    with the WL orbit codecs at wl_iter = 0 (src/recursive/mod.rs:117-148, src/recursive/graph/
+    incomplete.rs:189-236): ORBITS_DEGREE with the extra half iteration, ORBITS_ONE_CLASS without.
+    A symbol is the graph's edges as pairs (i, j), i <= j."""
+
+    def __init__(self, bernoulli, num_nodes, loops, orbits=ORBITS_NONE):
+        self.bernoulli, self.num_nodes, self.loops, self.orbits = bernoulli, num_nodes, bool(loops), int(orbits)
+
+    def push(self, m, x):
+        """Returns perm: perm[position] = the input node the push put there (the identity for NONE)."""
+        e = _edge_pairs(list(x))
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        _check(lib().ans_ar_er_push(m.h, _two_symbol_table(self.bernoulli).table, self.num_nodes, self.loops,
+                                    self.orbits, _np_ptr(e) if len(e) else None, len(e), _np_ptr(perm)),
+               "AutoregressiveER::push")
+        return perm[:self.num_nodes]
+
+    def pop(self, m, cap=None):
+        """The pairs of positions in pop order; the input relabelled by the push's perm."""
+        n = self.num_nodes
+        cap = n * (n - 1) // 2 + (n if self.loops else 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        count = sz(0)
+        _check(lib().ans_ar_er_pop(m.h, _two_symbol_table(self.bernoulli).table, n, self.loops, self.orbits,
+                                   _np_ptr(out), cap, ctypes.byref(count)), "AutoregressiveER::pop")
+        return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
 # ============================================================== GPU bulk path (section 4)
 def device_count():
     c = ci(0)
@@ -736,7 +780,7 @@ class Gpu:
 
     def last_launch_grid(self, index=0):
         """The workgroups of launch `index` of that record (ans_gpu_last_launch_grid): kept by the
-        multiset and Pólya urn kernels, 0 for the others; lanes = 64 x workgroups."""
+        multiset, Pólya urn and autoregressive Erdős–Rényi kernels, 0 for the others; lanes = 64 x workgroups."""
         wg = ctypes.c_uint32(0)
         _check(lib().ans_gpu_last_launch_grid(self.h, index, ctypes.byref(wg)), "ans_gpu_last_launch_grid")
         return wg.value
@@ -1406,6 +1450,82 @@ class GpuPolyaUrn:
         _check(lib().ans_dev_polya_pop(self.gpu.h, self.loops, self.redraws, num_graphs, _dptr(d_num_nodes),
                                        _dptr(d_edges), _dptr(d_edge_offsets), max_nodes, max_edges, _dptr(d_slots),
                                        slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_polya_pop")
+
+
+class GpuAutoregressiveER:
+    """AutoregressiveER in bulk (include/ans_capi.h 5d): graph g onto / from message g of a container,
+    one lane per graph, under the resume contract."""
+
+    def __init__(self, gpu, bernoulli, loops, orbits=ORBITS_NONE):
+        self.gpu, self.bernoulli = gpu, bernoulli
+        self.table = GpuTable(gpu, _two_symbol_table(bernoulli))
+        self.loops, self.orbits = int(bool(loops)), int(orbits)
+
+    def slack(self, max_nodes):
+        """Bytes a message can grow by during a push or a pop (slot_cap of dev_push / dev_pop)."""
+        b = u64(0)
+        _check(lib().ans_gpu_ar_er_slack(self.table.h, max_nodes, self.loops, ctypes.byref(b)), "ans_gpu_ar_er_slack")
+        return b.value
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        _check(fn(self.table.h, self.loops, self.orbits, num_graphs, *before, *after, _np_ptr(out), len(out),
+                  _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)), where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def push_graphs(self, num_nodes, edge_lists, data, offsets, lens):
+        """AutoregressiveER::push of graph g (edge_lists[g]: pairs) onto message g of the container
+        (data, offsets, lens), then flatten: returns (list of perms, container of the results)."""
+        where = "ans_gpu_ar_er_push_graphs"
+        lists = [_edge_pairs(e) for e in edge_lists]
+        nn, eo = GpuPolyaUrn._shapes(where, num_nodes, [len(e) for e in lists])
+        edges = np.ascontiguousarray(np.concatenate(lists)) if int(eo[-1]) else np.zeros((1, 2), np.uint32)
+        g = len(nn)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        width = int(nn.max()) if g else 0
+        perm = np.zeros((max(g, 1), max(width, 1)), np.uint32)
+        container = self._call(
+            where, lib().ans_gpu_ar_er_push_graphs, (_np_ptr(nn), _np_ptr(edges), _np_ptr(eo)),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(perm)), g,
+            data.size + g * self.slack(width))
+        return [perm[k, :int(nn[k])] for k in range(g)], container
+
+    def pop_graphs(self, num_nodes, data, offsets, lens, caps=None):
+        """AutoregressiveER::pop of graph g from message g; caps[g] bounds its pairs (default: every
+        pair of its alphabet).  Returns (list of (E_g, 2) arrays of positions, container of what remains)."""
+        where = "ans_gpu_ar_er_pop_graphs"
+        if caps is None:
+            caps = [int(n) * (int(n) - 1) // 2 + (int(n) if self.loops else 0) for n in num_nodes]
+        nn, eo = GpuPolyaUrn._shapes(where, num_nodes, caps)
+        g = len(nn)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        edges = np.zeros((max(int(eo[-1]), 1), 2), np.uint32)
+        counts = np.zeros(max(g, 1), np.uint32)
+        container = self._call(
+            where, lib().ans_gpu_ar_er_pop_graphs, (_np_ptr(nn), _np_ptr(eo)),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(edges),
+             _np_ptr(counts)), g, data.size + g * self.slack(int(nn.max()) if g else 0))
+        return [edges[int(eo[k]):int(eo[k]) + int(counts[k])] for k in range(g)], container
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None, d_perm=None):
+        """In place on device slots: d_lens is read and rewritten; d_perm (num_graphs * max_nodes) is optional."""
+        _check(lib().ans_dev_ar_er_push(self.table.h, self.loops, self.orbits, num_graphs, _dptr(d_num_nodes),
+                                        _dptr(d_edges), _dptr(d_edge_offsets), max_nodes, max_edges,
+                                        _dptr(d_perm) if d_perm is not None else None, _dptr(d_slots), slot_cap,
+                                        _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_ar_er_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, max_nodes, d_slots, slot_cap,
+                d_lens, d_status, stream=None):
+        """... d_edges receives graph g's pairs from d_edge_offsets[g] on (the offsets are capacities),
+        d_num_edges[g] their number."""
+        _check(lib().ans_dev_ar_er_pop(self.table.h, self.loops, self.orbits, num_graphs, _dptr(d_num_nodes),
+                                       _dptr(d_edges), _dptr(d_edge_offsets), _dptr(d_num_edges), max_nodes,
+                                       _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_ar_er_pop")
 
 
 # ============================================================== graph models' bulk caller (section 5)

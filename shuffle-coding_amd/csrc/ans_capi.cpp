@@ -8,6 +8,7 @@
 // for it.
 #include <new>
 
+#include "ans_arer.hpp"
 #include "ans_mset.hpp"
 #include "ans_polya.hpp"
 #include "ans_table.hpp"
@@ -342,6 +343,59 @@ int ans_polya_pop(ans_msg* m, uint32_t num_nodes, int loops, int redraws, uint32
     if (!m || (num_edges && !edges)) return ANS_E_ARG;
     return polya_host(m, num_nodes, num_edges, [&](auto& c, auto& st) {
         return polya::pop_graph(c, st, num_nodes, loops != 0, redraws != 0, edges, static_cast<uint32_t>(num_edges));
+    });
+}
+
+// ---- the autoregressive Erdős–Rényi graph codecs on one message (ans_arer.hpp):
+// Autoregressive(ErdosRenyiSliceCodecs) and ShuffleCodec<.., WLOrbitCodecs> with wl_iter = 0,
+// src/recursive/mod.rs:117-216, src/recursive/graph/slice.rs:16-59, incomplete.rs:189-236
+extern "C++" {
+namespace {
+struct SizedWs {  // ans_arer.hpp's states name each array's length; a vector needs only its start
+    uint32_t* p;
+    VecAcc at(uint64_t o, uint64_t) const { return VecAcc{p + o}; }
+};
+template <class F>
+int arer_host(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int orbits, F&& f) {
+    return guarded([&] {
+        if (bern->cat.masses.size() != 2) throw AnsError(ANS_E_ARG, "the indicator table needs exactly two symbols");
+        if (orbits != ANS_ORBITS_NONE && orbits != ANS_ORBITS_ONE_CLASS && orbits != ANS_ORBITS_DEGREE)
+            throw AnsError(ANS_E_ARG, "orbits outside NONE, ONE_CLASS, DEGREE");
+        if (num_nodes > 0x7FFFFFFFu) throw AnsError(ANS_E_ARG, "2^31 or more nodes");
+        std::vector<uint32_t> rank;
+        if (orbits == ANS_ORBITS_DEGREE && !arer::build_degree_ranks(num_nodes, rank))
+            throw AnsError(ANS_E_ARG, "two degrees share a class id");
+        const arer::Bern b = arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]);
+        HostMsg hm{m->m, m->m.head};
+        polya::Coder<HostMsg> c{hm, ANS_OK};
+        if (const int rc = f(c, b, rank.data())) throw AnsError(rc, ans_status_string(rc));
+    });
+}
+}  // namespace
+}  // extern "C++" (templates)
+
+int ans_ar_er_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int orbits, const uint32_t* edges,
+                   size_t num_edges, uint32_t* perm) {
+    if (!m || !bern || (num_edges && !edges) || num_edges > arer::kMaxEdges) return ANS_E_ARG;
+    return arer_host(m, bern, num_nodes, orbits, [&](auto& c, const arer::Bern& b, const uint32_t* rank) {
+        std::vector<uint32_t> ws(arer::push_entries(num_nodes, num_edges));
+        auto st = arer::PushState<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges);
+        return arer::push_graph(c, st, b, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, static_cast<uint32_t>(num_edges),
+                                perm);
+    });
+}
+
+int ans_ar_er_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int orbits, uint32_t* edges,
+                  size_t cap, size_t* num_edges) {
+    if (!m || !bern || !num_edges || (cap && !edges)) return ANS_E_ARG;
+    *num_edges = 0;
+    return arer_host(m, bern, num_nodes, orbits, [&](auto& c, const arer::Bern& b, const uint32_t* rank) {
+        std::vector<uint32_t> ws(arer::pop_entries(num_nodes));
+        auto st = arer::PopState<VecAcc>::make(SizedWs{ws.data()}, num_nodes);
+        uint64_t count = 0;
+        const int rc = arer::pop_graph(c, st, b, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, cap, &count);
+        *num_edges = static_cast<size_t>(count);
+        return rc;
     });
 }
 

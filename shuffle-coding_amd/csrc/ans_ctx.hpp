@@ -31,6 +31,8 @@ struct ans_gpu {
     LaunchLog last;  // the last launcher call's coder kernels (ans_gpu_last_launch)
     void* d_mset_ws = nullptr;  // per-lane counts of the multiset kernels' global form (ans_mset.hip)
     size_t cap_mset_ws = 0;
+    uint32_t* d_degree_rank = nullptr;  // class ranks of the degrees 0 .. n_degree_rank - 1 (ans_arer.hip)
+    uint32_t n_degree_rank = 0;
 };
 
 struct ans_gpu_table {
@@ -42,6 +44,7 @@ struct ans_gpu_table {
     FastTable ft;        // throughput path (ans_fast.hpp) when ft.usable
     void* d_fast;
     struct ans_gpu_tableset* ts64;  // norm >= 2^32 or nsym > 65536: the exact 64-bit kernels (ans_codecs.hip)
+    uint64_t mass2[2] = {0, 0};     // the masses of a table of two symbols (a Bernoulli; ans_arer.hip)
 };
 
 #define ANS_HIP_TRY(expr)                                                                              \

@@ -707,6 +707,8 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
         case kRecMsetPop: w = std::snprintf(o, room - 1, "k_mset_pop<%s,cnt=%s>", sym, a[0] ? "lds" : "global"); break;
         case kRecPolyaPush: w = std::snprintf(o, room - 1, "k_polya_push<redraws=%d>", a[0]); break;
         case kRecPolyaPop: w = std::snprintf(o, room - 1, "k_polya_pop<redraws=%d>", a[0]); break;
+        case kRecArerPush: w = std::snprintf(o, room - 1, "k_arer_push<orbits=%d>", a[0]); break;
+        case kRecArerPop: w = std::snprintf(o, room - 1, "k_arer_pop<orbits=%d>", a[0]); break;
         default: w = std::snprintf(o, room - 1, "?"); break;
         }
         at += static_cast<size_t>(w);
@@ -737,6 +739,7 @@ void ans_gpu_free(ans_gpu* g) try {
     ans_pipe_free(g);
     if (g->d_scratch) (void)hipFree(g->d_scratch);
     if (g->d_mset_ws) (void)hipFree(g->d_mset_ws);
+    if (g->d_degree_rank) (void)hipFree(g->d_degree_rank);
     (void)hipStreamDestroy(g->stream);
     delete g;
 } ANS_CATCH_VOID
@@ -759,6 +762,7 @@ int ans_gpu_table_create(ans_gpu* g, const ans_table* tab, ans_gpu_table** out) 
             ans_tableset_destroy(ts);
             return ANS_E_ALLOC;
         }
+        if (nsym == 2) std::copy_n(cat.masses.begin(), 2, gt->mass2);
         *out = gt;
         return ANS_OK;
     }
@@ -797,6 +801,7 @@ int ans_gpu_table_create(ans_gpu* g, const ans_table* tab, ans_gpu_table** out) 
     t.bucket = reinterpret_cast<const uint16_t*>(static_cast<char*>(mem) + rows_bytes);
     auto* gt = new (std::nothrow) ans_gpu_table{g, g->device, t, mem, 0, FastTable{}, nullptr, nullptr};
     if (!gt) { (void)hipFree(mem); return ANS_E_ALLOC; }
+    if (nsym == 2) std::copy_n(cat.masses.begin(), 2, gt->mass2);
     if (rows_bytes + bucket_bytes <= kLdsTableLimit) gt->lds_bytes = static_cast<uint32_t>(rows_bytes + bucket_bytes);
     const int rc = build_fast_table(gt, cat);
     if (rc) {

@@ -28,6 +28,8 @@ enum LaunchKind : uint8_t {
     kRecMsetPop,
     kRecPolyaPush,      // k_polya_push / k_polya_pop (ans_polya.hip)  a = {kRedraws, workgroups}
     kRecPolyaPop,
+    kRecArerPush,       // k_arer_push / k_arer_pop (ans_arer.hip)  a = {orbits, workgroups}
+    kRecArerPop,
 };
 struct LaunchRec {
     uint8_t kind;
@@ -37,7 +39,7 @@ struct LaunchRec {
 // The slot of a[] in which a record kind keeps its launch's workgroup count (ans_gpu_last_launch_grid
 // reads it; the text of ans_gpu_last_launch does not show it), or -1 for a kind that keeps none.
 constexpr int rec_grid_slot(uint8_t kind) {
-    return kind == kRecMsetPush || kind == kRecMsetPop || kind == kRecPolyaPush || kind == kRecPolyaPop ? 1 : -1;
+    return kind >= kRecMsetPush && kind <= kRecArerPop ? 1 : -1;
 }
 // ... and the count as the slot holds it: the workspace forms launch at most 8 workgroups per CU;
 // the LDS form of the multiset kernels, one lane per chunk, can pass an int16_t and saturates.
