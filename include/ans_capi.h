@@ -177,7 +177,8 @@ int ans_polya_pop(ans_msg *m, uint32_t num_nodes, int loops, int redraws, uint32
  * ANS_E_ARG: a table without exactly two symbols, an `orbits` outside the three values, 2^31 or
  * more pairs or nodes, or two degrees <= num_nodes with one class id (none below 70,000).
  * A failed call leaves the message wherever the failing step found it.  Deeper WL iterations,
- * PolyaUrnSliceCodecs, labels and directed graphs are not coded. */
+ * labels and directed graphs are not coded; PolyaUrnSliceCodecs is
+ * ans_ar_polya_push / _pop below. */
 #define ANS_ORBITS_NONE 0
 #define ANS_ORBITS_ONE_CLASS 1
 #define ANS_ORBITS_DEGREE 2
@@ -185,6 +186,27 @@ int ans_ar_er_push(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int lo
                    const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
 int ans_ar_er_pop(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int orbits, uint32_t *edges,
                   size_t cap, size_t *num_edges);
+/* The same graph under the autoregressive Pólya urn model: Autoregressive(PolyaUrnSliceCodecs)
+ * (src/recursive/graph/slice.rs:61-230; the harness's ord_AP) and ShuffleCodec<PolyaUrnSliceCodecs,
+ * WLOrbitCodecs<GraphPrefix>> with wl_iter = 0 (wl0r_AP / wl0-r_AP).  edges, perm, `orbits` and the
+ * order of the steps are those of ans_ar_er_push / _pop; only the slice's codec differs.  The slice of
+ * position v is the SET of its pairs (v, j), j among the unknown positions v+1 .. num_nodes-1 and v
+ * itself when `loops`, s_v = num_nodes - v - 1 + loops of them:
+ *   its size len under LogUniform(bitlen(s_v) + 1): b = bitlen(len) under Uniform(bitlen(s_v) + 2),
+ *   below it len - 2^(b-1) under Uniform(2^(b-1)) when b > 0;
+ *   if len > 0, multiset_shuffle_codec over the pairs (plain for len <= 11, joint with the orbit id
+ *   SipHash-1-3 of (v, j) beyond, as ans_polya_push) around the ordered codec: the j's are drawn
+ *   without replacement from the urn over the positions v + !loops .. num_nodes-1, mass(j) = 1 + the
+ *   number of j's neighbours among the positions < v (a loop counts once).
+ * pop: edges receives the pairs (v, w), v <= w, as positions: v ascending, within v by w ascending
+ * (the loop first), *num_edges their number; more than cap of them is ANS_E_LEN.
+ * ANS_E_SYMBOL: as ans_ar_er_push; pop: a decoded slice size above s_v (bytes no push wrote).
+ * ANS_E_ARG: an `orbits` outside the three values, 2^31 or more pairs or nodes, two degrees with one
+ * class id, or two pairs of one slice of 12 or more with one orbit id.  ANS_E_EXHAUSTED: as ans_cat_pop. */
+int ans_ar_polya_push(ans_msg *m, uint32_t num_nodes, int loops, int orbits, const uint32_t *edges,
+                      size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
+int ans_ar_polya_pop(ans_msg *m, uint32_t num_nodes, int loops, int orbits, uint32_t *edges, size_t cap,
+                     size_t *num_edges);
 
 /* ======================================================================
  * (4) GPU bulk path (MI355X / gfx950) — the data-parallel hot path.
@@ -244,9 +266,10 @@ int ans_gpu_table_paths(const ans_gpu_table *gt, uint32_t *paths);
  *   k_mset_push<u8,cnt=lds>   k_mset_pop<u16,cnt=global>      (cnt: where the per-lane counts live)
  *   k_polya_push<redraws=0>   k_polya_pop<redraws=1>          (section 5c)
  *   k_arer_push<orbits=2>   k_arer_pop<orbits=0>              (section 5d)
+ *   k_arpu_push<orbits=2>   k_arpu_pop<orbits=0>              (section 5e)
  * The calls that write it are the Categorical table's (sections 3 and 4: fixed, ragged and variable
  * chunks, host or device buffers; a pipelined host call leaves its last batch's launches), the
- * Independent ones (new messages and resume), the multiset ones, the Pólya urn ones and the autoregressive Erdős–Rényi ones; helper kernels (staging, compaction) are not named,
+ * Independent ones (new messages and resume), the multiset ones, the Pólya urn ones and the autoregressive Erdős–Rényi and Pólya urn ones; helper kernels (staging, compaction) are not named,
  * and the other calls (and calls that return before any launch: no symbols, bad arguments) leave
  * the record as it was.  Empty before the first such call.
  * Writes *len = the text's bytes (without the terminating NUL) and, if cap > *len, the
@@ -256,7 +279,7 @@ int ans_gpu_last_launch(const ans_gpu *g, char *buf, size_t cap, size_t *len);
 /* The workgroup count of launch `index` (0-based, in launch order) of the same record.  Kept for
  * the kernels whose lanes are bounded by a workspace of the context's, where one lane codes several
  * items in turn: k_mset_push / k_mset_pop (saturating at 32,767: the cnt=lds form launches one
- * lane per chunk), k_polya_push / k_polya_pop and k_arer_push / k_arer_pop; *workgroups = 0 for the other kernels, whose
+ * lane per chunk), k_polya_push / k_polya_pop, k_arer_push / k_arer_pop and k_arpu_push / k_arpu_pop; *workgroups = 0 for the other kernels, whose
  * records do not keep it.  Lanes = 64 x workgroups.  ANS_E_ARG for an index at or past the
  * launches recorded.  For tests and tuning, as the text is. */
 int ans_gpu_last_launch_grid(const ans_gpu *g, uint32_t index, uint32_t *workgroups);
@@ -798,6 +821,50 @@ int ans_gpu_ar_er_pop_graphs(ans_gpu_table *gt, int loops, int orbits, uint64_t 
                              const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges,
                              uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
                              uint64_t *lens, uint64_t *total);
+
+/* ======================================================================
+ * (5e) The autoregressive Pólya urn graph codecs in bulk: ans_ar_polya_push / ans_ar_polya_pop
+ *      (section 3) of graph g onto / from the message ALREADY in slot g, one lane per graph, under
+ *      the resume contract exactly as section 5d has it (slots, d_lens, d_perm, the offsets as
+ *      CAPACITIES on a pop, d_num_edges, the statuses OR-ed into *d_status with d_lens[g] = 0 for the
+ *      failing graph alone).  The bytes equal the host codec's.  The model has no parameters, so the
+ *      calls take the context where section 5d takes the table.
+ *      ANS_E_ARG for a graph of more than max_nodes nodes or (push) max_edges pairs; ANS_E_LEN for a
+ *      result past slot_cap, a d_lens[g] above it, or more pairs than the graph's capacity.  With
+ *      slot_cap >= d_lens[g] + ans_gpu_ar_polya_slack(max_nodes, max_edges) neither call meets
+ *      ANS_E_LEN for a slot (pop: max_edges bounds the pairs a graph can hold, its capacity at most):
+ *      with bn = bitlen(max_nodes) the slack is
+ *        max(max_nodes * (bitlen(bn + 2) + bn) + max_edges * bitlen(max_nodes + max_edges),
+ *            (max_nodes + max_edges) * bn) / 8 + 1 + (2 max_nodes + 2 max_edges) / 2^20 + 16 bytes
+ *      (DESIGN.md section 3.11).  The host-buffer calls apply it.
+ *      The per-lane state (push: 13 max_nodes + 2 max_edges + 2 dwords, pop: 9 max_nodes + min(max_nodes, 11) + 1) lives
+ *      in the workspace of sections 4b / 5c / 5d under the same rule, at most 256 MiB; bounds whose
+ *      single wave passes that are ANS_E_ARG before anything is launched or recorded, as are
+ *      max_edges >= 2^31.  The degrees' class ranks are the table of section 5d.
+ *      Kernel names in ans_gpu_last_launch: k_arpu_push<orbits=2>, k_arpu_pop<orbits=0>, their
+ *      workgroups in ans_gpu_last_launch_grid.
+ * ====================================================================== */
+int ans_gpu_ar_polya_slack(uint32_t max_nodes, uint64_t max_edges, uint64_t *bytes);
+int ans_dev_ar_polya_push(ans_gpu *g, int loops, int orbits, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                          const uint32_t *d_edges, const uint64_t *d_edge_offsets, uint32_t max_nodes,
+                          uint64_t max_edges, uint32_t *d_perm /* NULL or num_graphs * max_nodes */,
+                          uint8_t *d_slots, uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status,
+                          void *stream);
+int ans_dev_ar_polya_pop(ans_gpu *g, int loops, int orbits, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                         uint32_t *d_edges /* out */, const uint64_t *d_edge_offsets /* capacities */,
+                         uint32_t *d_num_edges /* out */, uint32_t max_nodes, uint64_t max_edges /* the slack's */,
+                         uint8_t *d_slots /* in/out */, uint64_t slot_cap, uint32_t *d_lens /* in/out */,
+                         uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, exactly as ans_gpu_ar_er_push_graphs / _pop_graphs. */
+int ans_gpu_ar_polya_push_graphs(ans_gpu *g, int loops, int orbits, uint64_t num_graphs, const uint32_t *num_nodes,
+                                 const uint32_t *edges, const uint64_t *edge_offsets, const uint8_t *in,
+                                 uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *perm,
+                                 uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_ar_polya_pop_graphs(ans_gpu *g, int loops, int orbits, uint64_t num_graphs, const uint32_t *num_nodes,
+                                const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                                const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges,
+                                uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
+                                uint64_t *lens, uint64_t *total);
 
 #ifdef __cplusplus
 }

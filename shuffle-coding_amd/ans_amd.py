@@ -166,6 +166,13 @@ SIGNATURES = {
     "ans_dev_ar_er_pop": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, vp, u64, vp, vp, vp]),
     "ans_gpu_ar_er_push_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_ar_er_pop_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_ar_polya_push": (ci, [vp, ctypes.c_uint32, ci, ci, vp, sz, vp]),
+    "ans_ar_polya_pop": (ci, [vp, ctypes.c_uint32, ci, ci, vp, sz, ctypes.POINTER(sz)]),
+    "ans_gpu_ar_polya_slack": (ci, [ctypes.c_uint32, u64, u64p]),
+    "ans_dev_ar_polya_push": (ci, [vp, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_polya_pop": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_gpu_ar_polya_push_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_polya_pop_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
     "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
     "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
@@ -735,6 +742,35 @@ class AutoregressiveER(Codec):
         return [(int(i), int(j)) for i, j in out[:count.value]]
 
 
+class AutoregressivePolya(Codec):
+    """An undirected, unlabelled graph under the autoregressive Pólya urn model, on the host through
+    ans_ar_polya_push / ans_ar_polya_pop: Autoregressive(PolyaUrnSliceCodecs) for orbits = ORBITS_NONE
+    (src/recursive/mod.rs:190-216, src/recursive/graph/slice.rs:61-230), else recursive shuffle coding
+    with the WL orbit codecs at wl_iter = 0 as AutoregressiveER has them.  A symbol is the graph's edges
+    as pairs (i, j), i <= j.  The model has no parameters."""
+
+    def __init__(self, num_nodes, loops, orbits=ORBITS_NONE):
+        self.num_nodes, self.loops, self.orbits = num_nodes, bool(loops), int(orbits)
+
+    def push(self, m, x):
+        """Returns perm: perm[position] = the input node the push put there (the identity for NONE)."""
+        e = _edge_pairs(list(x))
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        _check(lib().ans_ar_polya_push(m.h, self.num_nodes, self.loops, self.orbits, _np_ptr(e) if len(e) else None,
+                                       len(e), _np_ptr(perm)), "AutoregressivePolya::push")
+        return perm[:self.num_nodes]
+
+    def pop(self, m, cap=None):
+        """The pairs of positions, sorted; the input relabelled by the push's perm."""
+        n = self.num_nodes
+        cap = n * (n - 1) // 2 + (n if self.loops else 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        count = sz(0)
+        _check(lib().ans_ar_polya_pop(m.h, n, self.loops, self.orbits, _np_ptr(out), cap, ctypes.byref(count)),
+               "AutoregressivePolya::pop")
+        return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
 # ============================================================== GPU bulk path (section 4)
 def device_count():
     c = ci(0)
@@ -780,7 +816,8 @@ class Gpu:
 
     def last_launch_grid(self, index=0):
         """The workgroups of launch `index` of that record (ans_gpu_last_launch_grid): kept by the
-        multiset, Pólya urn and autoregressive Erdős–Rényi kernels, 0 for the others; lanes = 64 x workgroups."""
+        multiset, Pólya urn and autoregressive (Erdős–Rényi, Pólya urn) kernels, 0 for the others; lanes = 64 x
+        workgroups."""
         wg = ctypes.c_uint32(0)
         _check(lib().ans_gpu_last_launch_grid(self.h, index, ctypes.byref(wg)), "ans_gpu_last_launch_grid")
         return wg.value
@@ -1526,6 +1563,83 @@ class GpuAutoregressiveER:
                                        _dptr(d_edges), _dptr(d_edge_offsets), _dptr(d_num_edges), max_nodes,
                                        _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
                "ans_dev_ar_er_pop")
+
+
+class GpuAutoregressivePolya:
+    """AutoregressivePolya in bulk (include/ans_capi.h 5e): graph g onto / from message g of a
+    container, one lane per graph, under the resume contract."""
+
+    def __init__(self, gpu, loops, orbits=ORBITS_NONE):
+        self.gpu, self.loops, self.orbits = gpu, int(bool(loops)), int(orbits)
+
+    @staticmethod
+    def slack(max_nodes, max_edges):
+        """Bytes a message can grow by during a push or a pop (slot_cap of dev_push / dev_pop)."""
+        b = u64(0)
+        _check(lib().ans_gpu_ar_polya_slack(max_nodes, max_edges, ctypes.byref(b)), "ans_gpu_ar_polya_slack")
+        return b.value
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        _check(fn(self.gpu.h, self.loops, self.orbits, num_graphs, *before, *after, _np_ptr(out), len(out),
+                  _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)), where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def push_graphs(self, num_nodes, edge_lists, data, offsets, lens):
+        """AutoregressivePolya::push of graph g (edge_lists[g]: pairs) onto message g of the container
+        (data, offsets, lens), then flatten: returns (list of perms, container of the results)."""
+        where = "ans_gpu_ar_polya_push_graphs"
+        lists = [_edge_pairs(e) for e in edge_lists]
+        nn, eo = GpuPolyaUrn._shapes(where, num_nodes, [len(e) for e in lists])
+        edges = np.ascontiguousarray(np.concatenate(lists)) if int(eo[-1]) else np.zeros((1, 2), np.uint32)
+        g = len(nn)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        width = int(nn.max()) if g else 0
+        most = int(np.diff(eo).max()) if g else 0
+        perm = np.zeros((max(g, 1), max(width, 1)), np.uint32)
+        container = self._call(
+            where, lib().ans_gpu_ar_polya_push_graphs, (_np_ptr(nn), _np_ptr(edges), _np_ptr(eo)),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(perm)), g,
+            data.size + g * self.slack(width, most))
+        return [perm[k, :int(nn[k])] for k in range(g)], container
+
+    def pop_graphs(self, num_nodes, data, offsets, lens, caps=None):
+        """AutoregressivePolya::pop of graph g from message g; caps[g] bounds its pairs (default: every
+        pair of its alphabet).  Returns (list of (E_g, 2) arrays of positions, container of what remains)."""
+        where = "ans_gpu_ar_polya_pop_graphs"
+        if caps is None:
+            caps = [int(n) * (int(n) - 1) // 2 + (int(n) if self.loops else 0) for n in num_nodes]
+        nn, eo = GpuPolyaUrn._shapes(where, num_nodes, caps)
+        g = len(nn)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        edges = np.zeros((max(int(eo[-1]), 1), 2), np.uint32)
+        counts = np.zeros(max(g, 1), np.uint32)
+        most = int(np.diff(eo).max()) if g else 0
+        container = self._call(
+            where, lib().ans_gpu_ar_polya_pop_graphs, (_np_ptr(nn), _np_ptr(eo)),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(edges),
+             _np_ptr(counts)), g, data.size + g * self.slack(int(nn.max()) if g else 0, most))
+        return [edges[int(eo[k]):int(eo[k]) + int(counts[k])] for k in range(g)], container
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None, d_perm=None):
+        """In place on device slots: d_lens is read and rewritten; d_perm (num_graphs * max_nodes) is optional."""
+        _check(lib().ans_dev_ar_polya_push(self.gpu.h, self.loops, self.orbits, num_graphs, _dptr(d_num_nodes),
+                                           _dptr(d_edges), _dptr(d_edge_offsets), max_nodes, max_edges,
+                                           _dptr(d_perm) if d_perm is not None else None, _dptr(d_slots), slot_cap,
+                                           _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_ar_polya_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, max_nodes, max_edges, d_slots,
+                slot_cap, d_lens, d_status, stream=None):
+        """... d_edges receives graph g's pairs from d_edge_offsets[g] on (the offsets are capacities),
+        d_num_edges[g] their number; max_edges is the bound the slack was asked for."""
+        _check(lib().ans_dev_ar_polya_pop(self.gpu.h, self.loops, self.orbits, num_graphs, _dptr(d_num_nodes),
+                                          _dptr(d_edges), _dptr(d_edge_offsets), _dptr(d_num_edges), max_nodes,
+                                          max_edges, _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status),
+                                          _sptr(stream)), "ans_dev_ar_polya_pop")
 
 
 # ============================================================== graph models' bulk caller (section 5)

@@ -9,6 +9,7 @@
 #include <new>
 
 #include "ans_arer.hpp"
+#include "ans_arpu.hpp"
 #include "ans_mset.hpp"
 #include "ans_polya.hpp"
 #include "ans_table.hpp"
@@ -394,6 +395,53 @@ int ans_ar_er_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loo
         auto st = arer::PopState<VecAcc>::make(SizedWs{ws.data()}, num_nodes);
         uint64_t count = 0;
         const int rc = arer::pop_graph(c, st, b, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, cap, &count);
+        *num_edges = static_cast<size_t>(count);
+        return rc;
+    });
+}
+
+// ---- the autoregressive Pólya urn graph codecs on one message (ans_arpu.hpp):
+// Autoregressive(PolyaUrnSliceCodecs) and ShuffleCodec<.., WLOrbitCodecs> with wl_iter = 0,
+// src/recursive/mod.rs:117-216, src/recursive/graph/slice.rs:61-230, incomplete.rs:189-236
+extern "C++" {
+namespace {
+template <class F>
+int arpu_host(ans_msg* m, uint32_t num_nodes, int orbits, F&& f) {
+    return guarded([&] {
+        if (orbits != ANS_ORBITS_NONE && orbits != ANS_ORBITS_ONE_CLASS && orbits != ANS_ORBITS_DEGREE)
+            throw AnsError(ANS_E_ARG, "orbits outside NONE, ONE_CLASS, DEGREE");
+        if (num_nodes > 0x7FFFFFFFu) throw AnsError(ANS_E_ARG, "2^31 or more nodes");
+        std::vector<uint32_t> rank;
+        if (orbits == ANS_ORBITS_DEGREE && !arer::build_degree_ranks(num_nodes, rank))
+            throw AnsError(ANS_E_ARG, "two degrees share a class id");
+        HostMsg hm{m->m, m->m.head};
+        polya::Coder<HostMsg> c{hm, ANS_OK};
+        if (const int rc = f(c, rank.data())) throw AnsError(rc, ans_status_string(rc));
+    });
+}
+}  // namespace
+}  // extern "C++" (templates)
+
+int ans_ar_polya_push(ans_msg* m, uint32_t num_nodes, int loops, int orbits, const uint32_t* edges, size_t num_edges,
+                      uint32_t* perm) {
+    if (!m || (num_edges && !edges) || num_edges > arpu::kMaxEdges) return ANS_E_ARG;
+    return arpu_host(m, num_nodes, orbits, [&](auto& c, const uint32_t* rank) {
+        std::vector<uint32_t> ws(arpu::push_entries(num_nodes, num_edges));
+        auto st = arpu::PushState<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges);
+        return arpu::push_graph(c, st, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges,
+                                static_cast<uint32_t>(num_edges), perm);
+    });
+}
+
+int ans_ar_polya_pop(ans_msg* m, uint32_t num_nodes, int loops, int orbits, uint32_t* edges, size_t cap,
+                     size_t* num_edges) {
+    if (!m || !num_edges || (cap && !edges)) return ANS_E_ARG;
+    *num_edges = 0;
+    return arpu_host(m, num_nodes, orbits, [&](auto& c, const uint32_t* rank) {
+        std::vector<uint32_t> ws(arpu::pop_entries(num_nodes));
+        auto st = arpu::PopState<VecAcc>::make(SizedWs{ws.data()}, num_nodes);
+        uint64_t count = 0;
+        const int rc = arpu::pop_graph(c, st, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, cap, &count);
         *num_edges = static_cast<size_t>(count);
         return rc;
     });

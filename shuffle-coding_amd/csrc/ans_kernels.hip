@@ -709,6 +709,8 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
         case kRecPolyaPop: w = std::snprintf(o, room - 1, "k_polya_pop<redraws=%d>", a[0]); break;
         case kRecArerPush: w = std::snprintf(o, room - 1, "k_arer_push<orbits=%d>", a[0]); break;
         case kRecArerPop: w = std::snprintf(o, room - 1, "k_arer_pop<orbits=%d>", a[0]); break;
+        case kRecArpuPush: w = std::snprintf(o, room - 1, "k_arpu_push<orbits=%d>", a[0]); break;
+        case kRecArpuPop: w = std::snprintf(o, room - 1, "k_arpu_pop<orbits=%d>", a[0]); break;
         default: w = std::snprintf(o, room - 1, "?"); break;
         }
         at += static_cast<size_t>(w);

@@ -16,61 +16,16 @@
 #include "ans_ctx.hpp"
 #include "ans_exact.hpp"
 #include "ans_hostio.hpp"
+#include "ans_lane.hpp"
 #include "ans_polya.hpp"
 
 using namespace shuffle_coding::exact;
+using namespace shuffle_coding::lane;
 namespace pu = shuffle_coding::polya;
 
 namespace {
 
 #define HIP_TRY(expr) ANS_HIP_TRY(expr)
-
-constexpr size_t kWsMax = size_t(256) << 20;  // the workspace never passes this (as ans_mset.hip's)
-
-// entry i of this lane's array: a wave on one entry reads 64 consecutive dwords
-struct LaneAcc {
-    uint32_t* p;
-    uint64_t stride;
-    __device__ uint32_t load(uint32_t i) const { return p[i * stride]; }
-    __device__ void store(uint32_t i, uint32_t v) { p[i * stride] = v; }
-};
-struct LaneWs {
-    uint32_t* p;  // the workspace + the lane
-    uint64_t lanes;
-    __device__ LaneAcc at(uint64_t o) const { return LaneAcc{p + o * lanes, lanes}; }
-};
-
-// the message of a push: head + the sink (the renorm of k_mset_push)
-struct SinkMsg {
-    uint64_t head;
-    Sink* sink;
-    __device__ bool renorm(uint64_t min_head) {
-        while (head < min_head) {
-            uint32_t byte = 0;
-            if (!sink->pop(byte)) return false;  // src/ans.rs:144
-            head = (head << 8) | byte;
-        }
-        while ((head >> 8) >= min_head) {
-            sink->put(static_cast<uint32_t>(head));
-            head >>= 8;
-        }
-        return true;
-    }
-};
-// ... and of a pop: head + the resumed source
-struct SourceMsg {
-    uint64_t head;
-    RSource* src;
-    __device__ bool renorm(uint64_t min_head) {
-        while (head < min_head && src->pull(head)) {}
-        if (head < min_head) return false;
-        while ((head >> 8) >= min_head) {
-            src->unpop(static_cast<uint32_t>(head) & 0xFFu);
-            head >>= 8;
-        }
-        return true;
-    }
-};
 
 struct PolyaArgs {
     uint64_t num_graphs;
@@ -158,35 +113,13 @@ __global__ __launch_bounds__(kThreads) void k_polya_pop(PolyaArgs a, uint32_t* _
 }
 
 // ---- host side
-hipStream_t stream_of(const ans_gpu* g, void* stream) { return stream ? static_cast<hipStream_t>(stream) : g->stream; }
-
-// The launch: as many lanes as the device holds at two waves per SIMD, fewer while their state
-// passes kWsMax; ANS_E_ARG when one wave's does.
-int plan(ans_gpu* g, uint64_t num_graphs, uint32_t max_nodes, uint64_t max_edges, unsigned& grid, uint32_t*& ws) {
-    if (max_edges > pu::kMaxEdges) return ANS_E_ARG;
-    const size_t per_wave = size_t(4) * kThreads * pu::ws_entries(max_nodes, max_edges);
-    if (per_wave > kWsMax) return ANS_E_ARG;
-    const uint64_t blocks = (num_graphs + kThreads - 1) / kThreads;
-    const uint64_t want = std::min<uint64_t>({blocks, static_cast<uint64_t>(g->ncu) * 8, kWsMax / per_wave});
-    const size_t bytes = per_wave * want;
-    if (g->cap_mset_ws < bytes) {  // the multiset kernels' workspace: one at a time uses it
-        if (g->d_mset_ws) (void)hipFree(g->d_mset_ws);  // (waits for the kernels that use it)
-        g->d_mset_ws = nullptr;
-        g->cap_mset_ws = 0;
-        HIP_TRY(hipMalloc(&g->d_mset_ws, bytes));
-        g->cap_mset_ws = bytes;
-    }
-    ws = static_cast<uint32_t*>(g->d_mset_ws);
-    grid = static_cast<unsigned>(want);
-    return ANS_OK;
-}
-
 int dev_polya(bool push, ans_gpu* g, int loops, int redraws, uint64_t num_graphs, const uint32_t* d_num_nodes,
               uint32_t* d_edges, const uint64_t* d_edge_offsets, uint32_t max_nodes, uint64_t max_edges,
               uint8_t* d_slots, uint64_t slot_cap, uint32_t* d_lens, uint32_t* d_status, hipStream_t s) {
     unsigned grid = 0;
     uint32_t* ws = nullptr;
-    if (int rc = plan(g, num_graphs, max_nodes, max_edges, grid, ws)) return rc;
+    if (max_edges > pu::kMaxEdges) return ANS_E_ARG;
+    if (int rc = plan(g, num_graphs, pu::ws_entries(max_nodes, max_edges), grid, ws)) return rc;
     const PolyaArgs a{num_graphs, d_num_nodes, d_edge_offsets, max_nodes, max_edges, d_slots,
                       slot_cap,   d_lens,      d_status,       ws,        loops};
     g->last.clear();

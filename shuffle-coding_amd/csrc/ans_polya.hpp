@@ -140,37 +140,135 @@ ANS_MSET_HD void heapsort(Acc& a, uint32_t n, Less less) {
     }
 }
 
-// ord = the E edges of e (pairs) in ascending order: by orbit id when joint, else as tuples.
-// ANS_E_SYMBOL when a pair occurs twice (insert_plain_edge asserts, src/graph_codec.rs:257),
-// ANS_E_ARG when two different pairs share an orbit id (they would share an orbit; not built).
-template <class Acc>
-ANS_MSET_HD int rank_edges(State<Acc>& st, const uint32_t* e, uint32_t E, bool joint) {
+// ---- the outer layers of multiset_shuffle_codec over E distinct elements (src/recursive/
+// multiset.rs:126-136): plain_shuffle_codec for E <= 11, the joint recursive codec with singleton
+// orbits beyond.  Shared by this codec (the elements are the graph's pairs) and ans_arpu.hpp (the
+// pairs of one slice).  St has the members orb, ord, rop, por as State names them; ids is an accessor
+// of 2 E entries, idle outside rank_elements for the caller's other uses.
+
+// ord = the elements 0 .. E-1 in ascending order: by orbit id when joint (id_of(k), kept in ids as
+// (low, high)), else as tuples (tuple_less(a, b)).  ANS_E_SYMBOL when an element occurs twice
+// (same(a, b); insert_plain_edge asserts, src/graph_codec.rs:257), ANS_E_ARG when two different
+// elements share an orbit id (they would share an orbit; not built).
+template <class St, class Ids, class IdOf, class Less, class Same>
+ANS_MSET_HD int rank_elements(St& st, Ids& ids, uint32_t E, bool joint, IdOf id_of, Less tuple_less, Same same) {
     for (uint32_t k = 0; k < E; ++k) st.ord.store(k, k);
     if (joint) {
         for (uint32_t k = 0; k < E; ++k) {
-            const uint64_t id = edge_id(e[2 * uint64_t(k)], e[2 * uint64_t(k) + 1]);
-            st.next.store(2 * k, static_cast<uint32_t>(id));
-            st.next.store(2 * k + 1, static_cast<uint32_t>(id >> 32));
+            const uint64_t id = id_of(k);
+            ids.store(2 * k, static_cast<uint32_t>(id));
+            ids.store(2 * k + 1, static_cast<uint32_t>(id >> 32));
         }
-        const Acc& ids = st.next;
+        const Ids& rd = ids;
         heapsort(st.ord, E, [&](uint32_t a, uint32_t b) {
-            const uint32_t ha = ids.load(2 * a + 1), hb = ids.load(2 * b + 1);
-            return ha != hb ? ha < hb : ids.load(2 * a) < ids.load(2 * b);
+            const uint32_t ha = rd.load(2 * a + 1), hb = rd.load(2 * b + 1);
+            return ha != hb ? ha < hb : rd.load(2 * a) < rd.load(2 * b);
         });
     } else {
-        heapsort(st.ord, E, [&](uint32_t a, uint32_t b) {
-            const uint32_t ia = e[2 * uint64_t(a)], ib = e[2 * uint64_t(b)];
-            return ia != ib ? ia < ib : e[2 * uint64_t(a) + 1] < e[2 * uint64_t(b) + 1];
-        });
+        heapsort(st.ord, E, tuple_less);
     }
     for (uint32_t r = 1; r < E; ++r) {
-        const uint64_t a = st.ord.load(r - 1), b = st.ord.load(r);
-        const bool same = e[2 * a] == e[2 * b] && e[2 * a + 1] == e[2 * b + 1];
-        if (same) return ANS_E_SYMBOL;
-        if (joint && st.next.load(2 * a) == st.next.load(2 * b) && st.next.load(2 * a + 1) == st.next.load(2 * b + 1))
+        const uint32_t a = st.ord.load(r - 1), b = st.ord.load(r);
+        if (same(a, b)) return ANS_E_SYMBOL;
+        if (joint && ids.load(2 * a) == ids.load(2 * b) && ids.load(2 * a + 1) == ids.load(2 * b + 1))
             return ANS_E_ARG;
     }
     return ANS_OK;
+}
+template <class Acc>
+ANS_MSET_HD int rank_edges(State<Acc>& st, const uint32_t* e, uint32_t E, bool joint) {
+    return rank_elements(
+        st, st.next, E, joint, [&](uint32_t k) { return edge_id(e[2 * uint64_t(k)], e[2 * uint64_t(k) + 1]); },
+        [&](uint32_t a, uint32_t b) {
+            const uint32_t ia = e[2 * uint64_t(a)], ib = e[2 * uint64_t(b)];
+            return ia != ib ? ia < ib : e[2 * uint64_t(a) + 1] < e[2 * uint64_t(b) + 1];
+        },
+        [&](uint32_t a, uint32_t b) {
+            return e[2 * uint64_t(a)] == e[2 * uint64_t(b)] && e[2 * uint64_t(a) + 1] == e[2 * uint64_t(b) + 1];
+        });
+}
+
+// The push side, after rank_elements: pops the order the ordered codec will see; rop[p] = the
+// element at position p of the permuted vector.  Returns a status.
+template <class M, class St>
+ANS_MSET_HD int shuffle_push(Coder<M>& c, St& st, uint32_t E, bool joint) {
+    if (!joint) {
+        // plain_shuffle_codec (src/plain/mod.rs:111-116): canonized() sorts; the group is trivial,
+        // so RCosetUniform::pop is PermutationUniform{E}::pop and E Uniform(1) pushes
+        for (uint32_t k = 0; k < E; ++k) st.por.store(k, k);
+        for (uint32_t k = E; k-- > 0;) {
+            const uint32_t x = static_cast<uint32_t>(c.pop_uniform(k + 1));
+            const uint32_t a = st.por.load(k), b = st.por.load(x);
+            st.por.store(k, b);
+            st.por.store(x, a);
+        }
+        for (uint32_t k = 0; k < E; ++k) c.push_uniform(1, 0);
+        if (c.err) return c.err;
+        // perm * x (_permuted_from_swap, src/permutable.rs:26-41): the k-th smallest goes to perm[k]
+        for (uint32_t k = 0; k < E; ++k) st.rop.store(st.por.load(k), st.ord.load(k));
+    } else {
+        // PrefixShuffleCodec::push (src/recursive/mod.rs:117-134) with unit slices (joint.rs) and
+        // singleton orbits (multiset.rs:105-124): position p starts with the element of rank p
+        st.orb.nsym = E;
+        for (uint32_t r = 0; r < E; ++r) {
+            st.orb.a.store(r, 1);
+            st.rop.store(r, r);
+            st.por.store(r, r);
+        }
+        st.orb.build();
+        for (uint32_t L = E; L > 0; --L) {
+            uint64_t q = 0, cf = 0;
+            if (!c.pop_begin(L, q, cf)) return c.err;
+            const uint32_t r = st.orb.find(cf).rank;
+            c.pop_end(1, q, 0);
+            const uint32_t at = st.por.load(r), last = L - 1, r2 = st.rop.load(last);
+            st.rop.store(at, r2);
+            st.por.store(r2, at);
+            st.rop.store(last, r);
+            st.por.store(r, last);
+            st.orb.add(r, -1);
+        }
+        for (uint32_t p = 0; p < E; ++p) st.rop.store(p, st.ord.load(st.rop.load(p)));
+    }
+    return ANS_OK;
+}
+
+// The pop side, after the ordered codec's pop and rank_elements of what it returned (element k =
+// the k-th popped): pushes the order back.  Returns a status.
+template <class M, class St>
+ANS_MSET_HD int shuffle_pop(Coder<M>& c, St& st, uint32_t E, bool joint) {
+    if (!joint) {
+        // plain_shuffle_codec's pop (src/plain/mod.rs:118-123): canon^-1 = ord; RCosetUniform::push
+        // is E Uniform(1) pops and PermutationUniform{E}::push (src/permutable.rs:184-200)
+        for (uint32_t k = 0; k < E; ++k) c.pop_uniform(1);
+        for (uint32_t k = 0; k < E; ++k) {
+            st.rop.store(k, k);
+            st.por.store(k, k);
+        }
+        for (uint32_t k = E; k-- > 0;) {
+            const uint32_t xi = st.ord.load(k), x = st.por.load(xi), pk = st.rop.load(k);
+            const uint32_t a = st.por.load(pk);  // p_inv.swap(p * k, xi)
+            st.por.store(pk, x);
+            st.por.store(xi, a);
+            const uint32_t b = st.rop.load(x);  // p.swap(k, x)
+            st.rop.store(x, pk);
+            st.rop.store(k, b);
+            st.orb.a.store(k, x);
+        }
+        for (uint32_t k = 0; k < E; ++k) c.push_uniform(k + 1, st.orb.a.load(k));
+    } else {
+        // PrefixShuffleCodec::pop (src/recursive/mod.rs:136-148): element k joins, its orbit is pushed
+        for (uint32_t r = 0; r < E; ++r) st.rop.store(st.ord.load(r), r);
+        st.orb.nsym = E;
+        st.orb.clear();
+        for (uint32_t k = 0; k < E; ++k) {
+            const uint32_t r = st.rop.load(k);
+            st.orb.add(r, 1);
+            c.push(1, uint64_t(k) + 1, st.orb.prefix(r));
+            if (c.err) return c.err;
+        }
+    }
+    return c.err;
 }
 
 // ---- the graph the ordered codec keeps: PlainGraph + MutCategorical (src/graph_codec.rs:211-264)
@@ -321,44 +419,7 @@ ANS_MSET_HD int push_graph(Coder<M>& c, State<Acc>& st, uint32_t n, bool loops, 
     }
     const bool joint = E > kPlainMax;
     if (const int rc = rank_edges(st, e, E, joint)) return rc;
-    if (!joint) {
-        // plain_shuffle_codec (src/plain/mod.rs:111-116): canonized() sorts; the group is trivial,
-        // so RCosetUniform::pop is PermutationUniform{E}::pop and E Uniform(1) pushes
-        for (uint32_t k = 0; k < E; ++k) st.por.store(k, k);
-        for (uint32_t k = E; k-- > 0;) {
-            const uint32_t x = static_cast<uint32_t>(c.pop_uniform(k + 1));
-            const uint32_t a = st.por.load(k), b = st.por.load(x);
-            st.por.store(k, b);
-            st.por.store(x, a);
-        }
-        for (uint32_t k = 0; k < E; ++k) c.push_uniform(1, 0);
-        if (c.err) return c.err;
-        // perm * x (_permuted_from_swap, src/permutable.rs:26-41): the k-th smallest goes to perm[k]
-        for (uint32_t k = 0; k < E; ++k) st.rop.store(st.por.load(k), st.ord.load(k));
-    } else {
-        // PrefixShuffleCodec::push (src/recursive/mod.rs:117-134) with unit slices (joint.rs) and
-        // singleton orbits (multiset.rs:105-124): position p starts with the edge of rank p
-        st.orb.nsym = E;
-        for (uint32_t r = 0; r < E; ++r) {
-            st.orb.a.store(r, 1);
-            st.rop.store(r, r);
-            st.por.store(r, r);
-        }
-        st.orb.build();
-        for (uint32_t L = E; L > 0; --L) {
-            uint64_t q = 0, cf = 0;
-            if (!c.pop_begin(L, q, cf)) return c.err;
-            const uint32_t r = st.orb.find(cf).rank;
-            c.pop_end(1, q, 0);
-            const uint32_t at = st.por.load(r), last = L - 1, r2 = st.rop.load(last);
-            st.rop.store(at, r2);
-            st.por.store(r2, at);
-            st.rop.store(last, r);
-            st.por.store(r, last);
-            st.orb.add(r, -1);
-        }
-        for (uint32_t p = 0; p < E; ++p) st.rop.store(p, st.ord.load(st.rop.load(p)));
-    }
+    if (const int rc = shuffle_push(c, st, E, joint)) return rc;
     // PolyaUrnEdgeIndicesCodec::push (src/graph_codec.rs:318-326) of the permuted vector
     auto edge_at = [&](uint32_t p, uint32_t& i, uint32_t& j) {
         const uint64_t k = st.rop.load(p);
@@ -409,42 +470,13 @@ ANS_MSET_HD int pop_graph(Coder<M>& c, State<Acc>& st, uint32_t n, bool loops, b
     // (an edge decoded twice, possible with redraws alone, is found here, not at its insert: the
     // urn and the stacks hold a multigraph as well as a graph)
     if (const int rc = rank_edges(st, out, E, joint)) return rc;
-    if (!joint) {
-        // plain_shuffle_codec's pop (src/plain/mod.rs:118-123): canon^-1 = ord; RCosetUniform::push
-        // is E Uniform(1) pops and PermutationUniform{E}::push (src/permutable.rs:184-200)
-        for (uint32_t k = 0; k < E; ++k) c.pop_uniform(1);
-        for (uint32_t k = 0; k < E; ++k) {
-            st.rop.store(k, k);
-            st.por.store(k, k);
-        }
-        for (uint32_t k = E; k-- > 0;) {
-            const uint32_t xi = st.ord.load(k), x = st.por.load(xi), pk = st.rop.load(k);
-            const uint32_t a = st.por.load(pk);  // p_inv.swap(p * k, xi)
-            st.por.store(pk, x);
-            st.por.store(xi, a);
-            const uint32_t b = st.rop.load(x);  // p.swap(k, x)
-            st.rop.store(x, pk);
-            st.rop.store(k, b);
-            st.orb.a.store(k, x);
-        }
-        for (uint32_t k = 0; k < E; ++k) c.push_uniform(k + 1, st.orb.a.load(k));
-        if (c.err) return c.err;
+    if (const int rc = shuffle_pop(c, st, E, joint)) return rc;
+    if (!joint) {  // the pairs come back sorted
         for (uint32_t k = 0; k < 2 * E; ++k) st.next.store(k, out[k]);
         for (uint32_t r = 0; r < E; ++r) {
             const uint32_t k = st.ord.load(r);
             out[2 * r] = st.next.load(2 * k);
             out[2 * r + 1] = st.next.load(2 * k + 1);
-        }
-    } else {
-        // PrefixShuffleCodec::pop (src/recursive/mod.rs:136-148): edge k joins, its orbit is pushed
-        for (uint32_t r = 0; r < E; ++r) st.rop.store(st.ord.load(r), r);
-        st.orb.nsym = E;
-        st.orb.clear();
-        for (uint32_t k = 0; k < E; ++k) {
-            const uint32_t r = st.rop.load(k);
-            st.orb.add(r, 1);
-            c.push(1, uint64_t(k) + 1, st.orb.prefix(r));
-            if (c.err) return c.err;
         }
     }
     return ANS_OK;
