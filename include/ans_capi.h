@@ -176,9 +176,9 @@ int ans_polya_pop(ans_msg *m, uint32_t num_nodes, int loops, int redraws, uint32
  * ANS_E_ZERO_MASS: a needed symbol of mass 0, as ans_cat_push.  ANS_E_EXHAUSTED: as ans_cat_pop.
  * ANS_E_ARG: a table without exactly two symbols, an `orbits` outside the three values, 2^31 or
  * more pairs or nodes, or two degrees <= num_nodes with one class id (none below 70,000).
- * A failed call leaves the message wherever the failing step found it.  Deeper WL iterations,
- * labels and directed graphs are not coded; PolyaUrnSliceCodecs is
- * ans_ar_polya_push / _pop below. */
+ * A failed call leaves the message wherever the failing step found it.  Deeper WL iterations are
+ * ans_ar_er_wl_push / _pop below; labels and directed graphs are not coded;
+ * PolyaUrnSliceCodecs is ans_ar_polya_push / _pop below. */
 #define ANS_ORBITS_NONE 0
 #define ANS_ORBITS_ONE_CLASS 1
 #define ANS_ORBITS_DEGREE 2
@@ -207,6 +207,33 @@ int ans_ar_polya_push(ans_msg *m, uint32_t num_nodes, int loops, int orbits, con
                       size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
 int ans_ar_polya_pop(ans_msg *m, uint32_t num_nodes, int loops, int orbits, uint32_t *edges, size_t cap,
                      size_t *num_edges);
+/* The same two codecs up to the order of the nodes with Weisfeiler-Lehman orbits of any depth:
+ * ShuffleCodec<.., WLOrbitCodecs<GraphPrefix>> with num_iter = wl_iter (0 .. ANS_WL_MAX_ITER, else
+ * ANS_E_ARG) and extra_half_iter = half_iter (src/recursive/graph/incomplete.rs:45-57, 87-151,
+ * 189-236; the harness's wl<k>r_AE / wl<k>r_AP with the half iteration, wl<k>-r_.. without; its
+ * default is wl_iter 1 with the half iteration).  The steps, the slices, edges, perm, the order of
+ * the popped pairs and the statuses are those of ans_ar_er_push / _pop and ans_ar_polya_push / _pop
+ * under ANS_ORBITS_DEGREE; only the class of a known position differs.  With hash(words) =
+ * SipHash-1-3, keys 0, 0, over 8-byte words, deg(i) the neighbours of position i in the prefix
+ * graph (every edge with a known end; a loop counts once and makes its node its own neighbour):
+ *   h_0(i) = hash(0) for a known position, hash(1, i) for an unknown one; with half_iter then
+ *            hash(h_0(i), deg(i));
+ *   h_t+1(i) = hash(h_t(i), deg(i), h_t(j) for j adjacent to i in ascending order), t < wl_iter;
+ *   the class of i is the vector h_0(i) .. h_wl_iter(i), classes in ascending lexicographic order.
+ * wl_iter = 0 gives the bytes of ANS_ORBITS_DEGREE (half_iter) and ANS_ORBITS_ONE_CLASS (without).
+ * ANS_E_ARG also for 2 (wl_iter + 1) num_nodes >= 2^32 (the id words of a graph are indexed by 32 bits).
+ * The ids are carried from step to step (recomputed within distance wl_iter of a slice's nodes) and
+ * equal WLOrbitCodecs::apply of the prefix at every step.  Labels and directed graphs are not coded
+ * (DESIGN.md section 5). */
+#define ANS_WL_MAX_ITER 3
+int ans_ar_er_wl_push(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                      const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
+int ans_ar_er_wl_pop(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                     uint32_t *edges, size_t cap, size_t *num_edges);
+int ans_ar_polya_wl_push(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                         const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
+int ans_ar_polya_wl_pop(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, uint32_t *edges,
+                        size_t cap, size_t *num_edges);
 
 /* ======================================================================
  * (4) GPU bulk path (MI355X / gfx950) — the data-parallel hot path.
@@ -865,6 +892,70 @@ int ans_gpu_ar_polya_pop_graphs(ans_gpu *g, int loops, int orbits, uint64_t num_
                                 const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges,
                                 uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
                                 uint64_t *lens, uint64_t *total);
+
+/* ======================================================================
+ * (5f) The same codecs with Weisfeiler-Lehman orbits in bulk: ans_ar_er_wl_push / _pop and
+ *      ans_ar_polya_wl_push / _pop (section 3) of graph g onto / from the message ALREADY in slot g,
+ *      one lane per graph, under the resume contract exactly as sections 5d / 5e have it (slots,
+ *      d_lens, d_perm, the offsets as CAPACITIES on a pop, d_num_edges, the statuses OR-ed into
+ *      *d_status with d_lens[g] = 0 for the failing graph alone).  The bytes equal the host codec's.
+ *      wl_iter above ANS_WL_MAX_ITER is ANS_E_ARG.  A pop keeps the decoded prefix's adjacency, so
+ *      both pops take max_edges and hold min(capacity, max_edges) pairs of a graph; one more is
+ *      ANS_E_LEN for that graph.
+ *      Slack: an orbit step still pops under the norm L <= max_nodes on a push and pushes at most
+ *      bitlen(max_nodes) bits per node on a pop, whatever the classes are, so the derivations of
+ *      ans_gpu_ar_er_slack and ans_gpu_ar_polya_slack hold unchanged: with slot_cap >= d_lens[g] +
+ *      that slack neither call meets ANS_E_LEN for a slot.  The host-buffer calls apply it.
+ *      The per-lane state, with K = wl_iter + 1 and o = (2K + 4 + 2 (wl_iter > 0)) max_nodes dwords
+ *      of orbit stage (the ids, the ordered known positions and their inverse, the dirty list and
+ *      its stamps, the sort scratch): Erdős–Rényi push 4 max_nodes + 2 max_edges + 1 + o, pop
+ *      2 max_nodes + 2 max_edges + o; Pólya urn push 11 max_nodes + 2 max_edges + 1 + o, pop
+ *      9 max_nodes + min(max_nodes, 11) + 2 max_edges + o.  It lives in the workspace of sections
+ *      4b / 5c / 5d under the same rule, at most 256 MiB; bounds whose single wave passes that are
+ *      ANS_E_ARG before anything is launched or recorded, as are max_edges >= 2^31.
+ *      Kernel names in ans_gpu_last_launch: k_arer_wl_push(wl_iter=1,half_iter=1), k_arer_wl_pop(..),
+ *      k_arpu_wl_push(..), k_arpu_wl_pop(..), their workgroups in ans_gpu_last_launch_grid.
+ * ====================================================================== */
+int ans_dev_ar_er_wl_push(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                          const uint32_t *d_num_nodes, const uint32_t *d_edges, const uint64_t *d_edge_offsets,
+                          uint32_t max_nodes, uint64_t max_edges, uint32_t *d_perm /* NULL or num_graphs * max_nodes */,
+                          uint8_t *d_slots, uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status,
+                          void *stream);
+int ans_dev_ar_er_wl_pop(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                         const uint32_t *d_num_nodes, uint32_t *d_edges /* out */,
+                         const uint64_t *d_edge_offsets /* capacities */, uint32_t *d_num_edges /* out */,
+                         uint32_t max_nodes, uint64_t max_edges, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                         uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_ar_polya_wl_push(ans_gpu *g, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                             const uint32_t *d_num_nodes, const uint32_t *d_edges, const uint64_t *d_edge_offsets,
+                             uint32_t max_nodes, uint64_t max_edges, uint32_t *d_perm, uint8_t *d_slots,
+                             uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_ar_polya_wl_pop(ans_gpu *g, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                            const uint32_t *d_num_nodes, uint32_t *d_edges /* out */,
+                            const uint64_t *d_edge_offsets /* capacities */, uint32_t *d_num_edges /* out */,
+                            uint32_t max_nodes, uint64_t max_edges, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                            uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, exactly as ans_gpu_ar_er_push_graphs / _pop_graphs. */
+int ans_gpu_ar_er_wl_push_graphs(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                 const uint32_t *num_nodes, const uint32_t *edges, const uint64_t *edge_offsets,
+                                 const uint8_t *in, uint64_t in_len, const uint64_t *in_offsets,
+                                 const uint64_t *in_lens, uint32_t *perm, uint8_t *out, uint64_t out_cap,
+                                 uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_ar_er_wl_pop_graphs(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                const uint32_t *num_nodes, const uint64_t *edge_offsets, const uint8_t *in,
+                                uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens,
+                                uint32_t *out_edges, uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap,
+                                uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_ar_polya_wl_push_graphs(ans_gpu *g, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                    const uint32_t *num_nodes, const uint32_t *edges, const uint64_t *edge_offsets,
+                                    const uint8_t *in, uint64_t in_len, const uint64_t *in_offsets,
+                                    const uint64_t *in_lens, uint32_t *perm, uint8_t *out, uint64_t out_cap,
+                                    uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_ar_polya_wl_pop_graphs(ans_gpu *g, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                   const uint32_t *num_nodes, const uint64_t *edge_offsets, const uint8_t *in,
+                                   uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens,
+                                   uint32_t *out_edges, uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap,
+                                   uint64_t *offsets, uint64_t *lens, uint64_t *total);
 
 #ifdef __cplusplus
 }

@@ -173,6 +173,18 @@ SIGNATURES = {
     "ans_dev_ar_polya_pop": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
     "ans_gpu_ar_polya_push_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_ar_polya_pop_graphs": (ci, [vp, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_ar_er_wl_push": (ci, [vp, vp, ctypes.c_uint32, ci, ci, ci, vp, sz, vp]),
+    "ans_ar_er_wl_pop": (ci, [vp, vp, ctypes.c_uint32, ci, ci, ci, vp, sz, ctypes.POINTER(sz)]),
+    "ans_ar_polya_wl_push": (ci, [vp, ctypes.c_uint32, ci, ci, ci, vp, sz, vp]),
+    "ans_ar_polya_wl_pop": (ci, [vp, ctypes.c_uint32, ci, ci, ci, vp, sz, ctypes.POINTER(sz)]),
+    "ans_dev_ar_er_wl_push": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_er_wl_pop": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_polya_wl_push": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_polya_wl_pop": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_gpu_ar_er_wl_push_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_er_wl_pop_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_polya_wl_push_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_polya_wl_pop_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
     "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
     "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
@@ -768,6 +780,63 @@ class AutoregressivePolya(Codec):
         count = sz(0)
         _check(lib().ans_ar_polya_pop(m.h, n, self.loops, self.orbits, _np_ptr(out), cap, ctypes.byref(count)),
                "AutoregressivePolya::pop")
+        return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
+WL_MAX_ITER = 3  # ANS_WL_MAX_ITER
+
+
+class AutoregressiveERWL(AutoregressiveER):
+    """AutoregressiveER up to the order of the nodes with Weisfeiler-Lehman orbits of depth wl_iter
+    (0 .. WL_MAX_ITER), with or without the extra half iteration, through ans_ar_er_wl_push / _pop:
+    WLOrbitCodecs<GraphPrefix> (src/recursive/graph/incomplete.rs:45-57, 87-151, 189-236).  The
+    defaults are the reference's (src/benchmark.rs:691-692).  wl_iter = 0 gives the bytes of
+    ORBITS_DEGREE with the half iteration and of ORBITS_ONE_CLASS without."""
+
+    def __init__(self, bernoulli, num_nodes, loops, wl_iter=1, half_iter=True):
+        super().__init__(bernoulli, num_nodes, loops, ORBITS_DEGREE if half_iter else ORBITS_ONE_CLASS)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+
+    def push(self, m, x):
+        e = _edge_pairs(list(x))
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        _check(lib().ans_ar_er_wl_push(m.h, _two_symbol_table(self.bernoulli).table, self.num_nodes, self.loops,
+                                       self.wl_iter, self.half_iter, _np_ptr(e) if len(e) else None, len(e),
+                                       _np_ptr(perm)), "AutoregressiveERWL::push")
+        return perm[:self.num_nodes]
+
+    def pop(self, m, cap=None):
+        n = self.num_nodes
+        cap = n * (n - 1) // 2 + (n if self.loops else 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        count = sz(0)
+        _check(lib().ans_ar_er_wl_pop(m.h, _two_symbol_table(self.bernoulli).table, n, self.loops, self.wl_iter,
+                                      self.half_iter, _np_ptr(out), cap, ctypes.byref(count)), "AutoregressiveERWL::pop")
+        return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
+class AutoregressivePolyaWL(AutoregressivePolya):
+    """AutoregressivePolya with the orbits of AutoregressiveERWL, through ans_ar_polya_wl_push / _pop."""
+
+    def __init__(self, num_nodes, loops, wl_iter=1, half_iter=True):
+        super().__init__(num_nodes, loops, ORBITS_DEGREE if half_iter else ORBITS_ONE_CLASS)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+
+    def push(self, m, x):
+        e = _edge_pairs(list(x))
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        _check(lib().ans_ar_polya_wl_push(m.h, self.num_nodes, self.loops, self.wl_iter, self.half_iter,
+                                          _np_ptr(e) if len(e) else None, len(e), _np_ptr(perm)),
+               "AutoregressivePolyaWL::push")
+        return perm[:self.num_nodes]
+
+    def pop(self, m, cap=None):
+        n = self.num_nodes
+        cap = n * (n - 1) // 2 + (n if self.loops else 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        count = sz(0)
+        _check(lib().ans_ar_polya_wl_pop(m.h, n, self.loops, self.wl_iter, self.half_iter, _np_ptr(out), cap,
+                                         ctypes.byref(count)), "AutoregressivePolyaWL::pop")
         return [(int(i), int(j)) for i, j in out[:count.value]]
 
 
@@ -1640,6 +1709,74 @@ class GpuAutoregressivePolya:
                                           _dptr(d_edges), _dptr(d_edge_offsets), _dptr(d_num_edges), max_nodes,
                                           max_edges, _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status),
                                           _sptr(stream)), "ans_dev_ar_polya_pop")
+
+
+class GpuAutoregressiveERWL(GpuAutoregressiveER):
+    """AutoregressiveERWL in bulk (include/ans_capi.h 5f): GpuAutoregressiveER's calls with the
+    Weisfeiler-Lehman orbits of depth wl_iter; the slack is GpuAutoregressiveER's."""
+
+    def __init__(self, gpu, bernoulli, loops, wl_iter=1, half_iter=True):
+        super().__init__(gpu, bernoulli, loops, ORBITS_DEGREE if half_iter else ORBITS_ONE_CLASS)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        where = where.replace("ans_gpu_ar_er_", "ans_gpu_ar_er_wl_")  # the same arguments around the two settings
+        _check(getattr(lib(), where)(self.table.h, self.loops, self.wl_iter, self.half_iter, num_graphs, *before, *after,
+                                     _np_ptr(out), len(out), _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)), where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None, d_perm=None):
+        _check(lib().ans_dev_ar_er_wl_push(self.table.h, self.loops, self.wl_iter, self.half_iter, num_graphs,
+                                           _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets), max_nodes,
+                                           max_edges, _dptr(d_perm) if d_perm is not None else None, _dptr(d_slots),
+                                           slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_ar_er_wl_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, max_nodes, max_edges, d_slots,
+                slot_cap, d_lens, d_status, stream=None):
+        """... max_edges bounds the pairs a graph's state holds (its capacity at most)."""
+        _check(lib().ans_dev_ar_er_wl_pop(self.table.h, self.loops, self.wl_iter, self.half_iter, num_graphs,
+                                          _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets), _dptr(d_num_edges),
+                                          max_nodes, max_edges, _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status),
+                                          _sptr(stream)), "ans_dev_ar_er_wl_pop")
+
+
+class GpuAutoregressivePolyaWL(GpuAutoregressivePolya):
+    """AutoregressivePolyaWL in bulk (include/ans_capi.h 5f); the slack is GpuAutoregressivePolya's."""
+
+    def __init__(self, gpu, loops, wl_iter=1, half_iter=True):
+        super().__init__(gpu, loops, ORBITS_DEGREE if half_iter else ORBITS_ONE_CLASS)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        where = where.replace("ans_gpu_ar_polya_", "ans_gpu_ar_polya_wl_")
+        _check(getattr(lib(), where)(self.gpu.h, self.loops, self.wl_iter, self.half_iter, num_graphs, *before, *after,
+                                     _np_ptr(out), len(out), _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)), where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None, d_perm=None):
+        _check(lib().ans_dev_ar_polya_wl_push(self.gpu.h, self.loops, self.wl_iter, self.half_iter, num_graphs,
+                                              _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets), max_nodes,
+                                              max_edges, _dptr(d_perm) if d_perm is not None else None, _dptr(d_slots),
+                                              slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_ar_polya_wl_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, max_nodes, max_edges, d_slots,
+                slot_cap, d_lens, d_status, stream=None):
+        _check(lib().ans_dev_ar_polya_wl_pop(self.gpu.h, self.loops, self.wl_iter, self.half_iter, num_graphs,
+                                             _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets),
+                                             _dptr(d_num_edges), max_nodes, max_edges, _dptr(d_slots), slot_cap,
+                                             _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_ar_polya_wl_pop")
 
 
 # ============================================================== graph models' bulk caller (section 5)

@@ -13,6 +13,7 @@
 #include "ans_mset.hpp"
 #include "ans_polya.hpp"
 #include "ans_table.hpp"
+#include "ans_wl.hpp"
 
 using namespace shuffle_coding;
 
@@ -442,6 +443,76 @@ int ans_ar_polya_pop(ans_msg* m, uint32_t num_nodes, int loops, int orbits, uint
         auto st = arpu::PopState<VecAcc>::make(SizedWs{ws.data()}, num_nodes);
         uint64_t count = 0;
         const int rc = arpu::pop_graph(c, st, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, cap, &count);
+        *num_edges = static_cast<size_t>(count);
+        return rc;
+    });
+}
+
+// ---- the same with Weisfeiler-Lehman orbits at wl_iter <= ANS_WL_MAX_ITER (ans_wl.hpp):
+// incomplete.rs:45-57, 87-151, 189-236
+extern "C++" {
+namespace {
+template <class F>
+int wl_host(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int wl_iter, F&& f) {
+    return guarded([&] {
+        if (bern && bern->cat.masses.size() != 2) throw AnsError(ANS_E_ARG, "the indicator table needs exactly two symbols");
+        if (wl_iter < 0 || wl_iter > ANS_WL_MAX_ITER) throw AnsError(ANS_E_ARG, "wl_iter outside 0 .. ANS_WL_MAX_ITER");
+        if (!wl::nodes_ok(num_nodes, wl_iter)) throw AnsError(ANS_E_ARG, "2^31 or more nodes, or 2^32 or more id words");
+        const arer::Bern b = bern ? arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]) : arer::Bern{};
+        HostMsg hm{m->m, m->m.head};
+        polya::Coder<HostMsg> c{hm, ANS_OK};
+        if (const int rc = f(c, b)) throw AnsError(rc, ans_status_string(rc));
+    });
+}
+}  // namespace
+}  // extern "C++" (templates)
+
+int ans_ar_er_wl_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                      const uint32_t* edges, size_t num_edges, uint32_t* perm) {
+    if (!m || !bern || (num_edges && !edges) || num_edges > arer::kMaxEdges) return ANS_E_ARG;
+    return wl_host(m, bern, num_nodes, wl_iter, [&](auto& c, const arer::Bern& b) {
+        std::vector<uint32_t> ws(wl::er_push_entries(num_nodes, num_edges, wl_iter));
+        auto st = wl::ErPush<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges, wl_iter, half_iter != 0);
+        return wl::er_push_graph(c, st, b, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
+    });
+}
+
+int ans_ar_er_wl_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                     uint32_t* edges, size_t cap, size_t* num_edges) {
+    if (!m || !bern || !num_edges || (cap && !edges)) return ANS_E_ARG;
+    *num_edges = 0;
+    // (no graph holds more pairs than its alphabet: a larger cap sizes nothing)
+    const uint64_t all = uint64_t(num_nodes) * (num_nodes + 1) / 2, room = std::min<uint64_t>({cap, all, arer::kMaxEdges});
+    return wl_host(m, bern, num_nodes, wl_iter, [&](auto& c, const arer::Bern& b) {
+        std::vector<uint32_t> ws(wl::er_pop_entries(num_nodes, room, wl_iter));
+        auto st = wl::ErPop<VecAcc>::make(SizedWs{ws.data()}, num_nodes, room, wl_iter, half_iter != 0);
+        uint64_t count = 0;
+        const int rc = wl::er_pop_graph(c, st, b, num_nodes, loops != 0, edges, room, &count);
+        *num_edges = static_cast<size_t>(count);
+        return rc;
+    });
+}
+
+int ans_ar_polya_wl_push(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, const uint32_t* edges,
+                         size_t num_edges, uint32_t* perm) {
+    if (!m || (num_edges && !edges) || num_edges > arpu::kMaxEdges) return ANS_E_ARG;
+    return wl_host(m, nullptr, num_nodes, wl_iter, [&](auto& c, const arer::Bern&) {
+        std::vector<uint32_t> ws(wl::pu_push_entries(num_nodes, num_edges, wl_iter));
+        auto st = wl::PuPush<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges, wl_iter, half_iter != 0);
+        return wl::pu_push_graph(c, st, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
+    });
+}
+
+int ans_ar_polya_wl_pop(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, uint32_t* edges,
+                        size_t cap, size_t* num_edges) {
+    if (!m || !num_edges || (cap && !edges)) return ANS_E_ARG;
+    *num_edges = 0;
+    const uint64_t all = uint64_t(num_nodes) * (num_nodes + 1) / 2, room = std::min<uint64_t>({cap, all, arpu::kMaxEdges});
+    return wl_host(m, nullptr, num_nodes, wl_iter, [&](auto& c, const arer::Bern&) {
+        std::vector<uint32_t> ws(wl::pu_pop_entries(num_nodes, room, wl_iter));
+        auto st = wl::PuPop<VecAcc>::make(SizedWs{ws.data()}, num_nodes, room, wl_iter, half_iter != 0);
+        uint64_t count = 0;
+        const int rc = wl::pu_pop_graph(c, st, num_nodes, loops != 0, edges, room, &count);
         *num_edges = static_cast<size_t>(count);
         return rc;
     });

@@ -711,6 +711,10 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
         case kRecArerPop: w = std::snprintf(o, room - 1, "k_arer_pop<orbits=%d>", a[0]); break;
         case kRecArpuPush: w = std::snprintf(o, room - 1, "k_arpu_push<orbits=%d>", a[0]); break;
         case kRecArpuPop: w = std::snprintf(o, room - 1, "k_arpu_pop<orbits=%d>", a[0]); break;
+        case kRecArerWlPush: w = std::snprintf(o, room - 1, "k_arer_wl_push(wl_iter=%d,half_iter=%d)", a[0], a[2]); break;
+        case kRecArerWlPop: w = std::snprintf(o, room - 1, "k_arer_wl_pop(wl_iter=%d,half_iter=%d)", a[0], a[2]); break;
+        case kRecArpuWlPush: w = std::snprintf(o, room - 1, "k_arpu_wl_push(wl_iter=%d,half_iter=%d)", a[0], a[2]); break;
+        case kRecArpuWlPop: w = std::snprintf(o, room - 1, "k_arpu_wl_pop(wl_iter=%d,half_iter=%d)", a[0], a[2]); break;
         default: w = std::snprintf(o, room - 1, "?"); break;
         }
         at += static_cast<size_t>(w);
