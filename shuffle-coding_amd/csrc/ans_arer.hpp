@@ -5,8 +5,10 @@
 // src/recursive/graph/incomplete.rs:189-236), one graph on one message.  Plain C++ templated on the
 // message and on how a per-graph array is read and written, host and device alike, so that the host
 // codec (ans_capi.cpp), the kernels (ans_arer.hip) and the CPU tests (g++, tests/native/
-// arer_state_check.cpp) run the same functions.  DESIGN.md §3.10 has the restatement with its
-// sources; the comments here say which reference line a step is.
+// arer_state_check.cpp) run the same functions.  The recursion is ans_rgraph.hpp's; this header has
+// its Erdős–Rényi slice model (ErSlices) and the orbit stage of wl_iter = 0 (CountPush / CountPop),
+// which ans_arpu.hpp uses too.  DESIGN.md §3.10 has the restatement with its sources; the comments
+// here say which reference line a step is.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -15,11 +17,12 @@
 
 #include "../../include/ans_capi.h"
 #include "ans_polya.hpp"
+#include "ans_rgraph.hpp"
 
 namespace shuffle_coding {
 namespace arer {
 
-constexpr uint64_t kMaxEdges = polya::kMaxEdges;  // the adjacency entries 2e, 2e + 1 stay below 2^32
+constexpr uint64_t kMaxEdges = rgraph::kMaxEdges;
 
 // The class of a known node of degree d (a loop counts once): at wl_iter = 0 with the extra half
 // iteration, hash((h0, vec![&(); d])) with h0 = hash(((), None::<usize>))
@@ -75,179 +78,146 @@ ANS_MSET_HD uint32_t pop_bit(polya::Coder<M>& c, const Bern& b) {  // src/ans.rs
     return x;
 }
 
-// The per-graph state of a push, u32 entries: Ws::at(offset, count) is an accessor (load / store, as
-// mset::Counts takes) of `count` entries from `offset` on.
-//   pos_of   the position of an input node;  node_at its inverse (the result is perm = node_at)
-//   off, nbr the adjacency in input labels as a CSR built from the pairs: node v's neighbours are
-//            nbr[off[v] .. off[v + 1]) (a loop names v once)
-//   mark     per node, the stamp that finds a pair given twice; then per position, the stamp of the
-//            step whose slice holds it
-//   rk       the class rank of the node at a position;  cnt the orbit counts per rank (a Fenwick tree)
-constexpr uint64_t push_entries(uint64_t max_nodes, uint64_t max_edges) { return 6 * max_nodes + 2 * max_edges + 2; }
+// ---- the slice model: IID<Bernoulli> over a node's pairs (slice.rs:16-59).  mark (a push alone):
+// per position, the stamp of the step whose slice holds it; before the first step the stamps that
+// find a pair given twice.  bern is the caller's to set.
 template <class Acc>
-struct PushState {
-    Acc pos_of, node_at, off, nbr, mark, rk;
-    mset::Counts<Acc> cnt;
-    template <class Ws>
-    ANS_MSET_HD static PushState make(const Ws& ws, uint64_t max_nodes, uint64_t max_edges) {
-        uint64_t o = 0;
-        auto take = [&](uint64_t n) {
-            const uint64_t at = o;
-            o += n;
-            return ws.at(at, n);
-        };
-        PushState s{take(max_nodes),     take(max_nodes), take(max_nodes + 1),     take(2 * max_edges),
-                    take(max_nodes),     take(max_nodes), {take(max_nodes + 1), 0}};
+struct ErSlices {
+    Acc mark;
+    Bern bern;
+    template <class T>
+    ANS_MSET_HD static ErSlices make(T& take, uint64_t max_nodes, bool push) {
+        ErSlices s{push ? take(max_nodes) : Acc{}, Bern{}};
         return s;
     }
-};
-// ... and of a pop: the degree so far per position and the orbit counts, nothing sized by the edges
-constexpr uint64_t pop_entries(uint64_t max_nodes) { return 2 * max_nodes + 1; }
-template <class Acc>
-struct PopState {
-    Acc deg;
-    mset::Counts<Acc> cnt;
-    template <class Ws>
-    ANS_MSET_HD static PopState make(const Ws& ws, uint64_t max_nodes) {
-        PopState s{ws.at(0, max_nodes), {ws.at(max_nodes, max_nodes + 1), 0}};
-        return s;
+    ANS_MSET_HD Acc& scratch() { return mark; }
+    ANS_MSET_HD void start_push(uint32_t n) {
+        for (uint32_t v = 0; v < n; ++v) mark.store(v, 0);
     }
-};
-
-// The class rank of a known node of degree d under `orbits` (ONE_CLASS: every known node has id h0,
-// incomplete.rs:193-196 without the half iteration); the counts span nranks ranks (the table's
-// entries) under DEGREE and one otherwise.
-template <class Rank>
-ANS_MSET_HD uint32_t class_rank(int orbits, const Rank& rank, uint32_t degree) {
-    return orbits == ANS_ORBITS_DEGREE ? rank[degree] : 0;
-}
-
-// ---- push.  e: the E pairs; n nodes; rank: build_degree_ranks of some max_nodes >= n, nranks =
-// max_nodes + 1 its entries (DEGREE alone reads it; the counts span its ranks); perm: null, or n
-// entries out, perm[position] = input node.  Returns a status.
-template <class M, class Acc, class Rank>
-ANS_MSET_HD int push_graph(polya::Coder<M>& c, PushState<Acc>& st, const Bern& b, uint32_t n, bool loops, int orbits,
-                           const Rank& rank, uint32_t nranks, const uint32_t* e, uint32_t E, uint32_t* perm) {
-    // the adjacency: degrees into off, their running sums (off[v] = v's end), the fill moves each
-    // off[v] down to v's start
-    for (uint32_t v = 0; v <= n; ++v) st.off.store(v, 0);
-    for (uint32_t k = 0; k < E; ++k) {
-        const uint32_t i = e[2 * uint64_t(k)], j = e[2 * uint64_t(k) + 1];
-        if (i > j || j >= n || (i == j && !loops)) return ANS_E_SYMBOL;  // src/graph_codec.rs:136
-        st.off.store(i, st.off.load(i) + 1);
-        if (i != j) st.off.store(j, st.off.load(j) + 1);
+    ANS_MSET_HD void gather(uint32_t, uint32_t p, uint32_t L) { mark.store(p, L); }
+    // IID<Bernoulli>::push over (L-1, L) .. (L-1, n-1), then the loop: last entry first
+    template <class M, class G>
+    ANS_MSET_HD int push(polya::Coder<M>& c, const G&, uint32_t n, bool loops, uint32_t last, uint32_t) {
+        const uint32_t L = last + 1;
+        if (loops) push_bit(c, bern, mark.load(last) == L);
+        for (uint32_t j = n; j-- > L;) push_bit(c, bern, mark.load(j) == L);
+        return c.err;
     }
-    uint32_t sum = 0;
-    for (uint32_t v = 0; v < n; ++v) {
-        sum += st.off.load(v);
-        st.off.store(v, sum);
-    }
-    st.off.store(n, sum);
-    for (uint32_t k = 0; k < E; ++k) {
-        const uint32_t i = e[2 * uint64_t(k)], j = e[2 * uint64_t(k) + 1];
-        uint32_t at = st.off.load(i) - 1;
-        st.off.store(i, at);
-        st.nbr.store(at, j);
-        if (i != j) {
-            at = st.off.load(j) - 1;
-            st.off.store(j, at);
-            st.nbr.store(at, i);
-        }
-    }
-    // a pair given twice names a neighbour twice (Graph::new's insert asserts, src/graph.rs)
-    for (uint32_t v = 0; v < n; ++v) st.mark.store(v, 0);
-    for (uint32_t v = 0; v < n; ++v)
-        for (uint32_t a = st.off.load(v), end = st.off.load(v + 1); a < end; ++a) {
-            const uint32_t w = st.nbr.load(a);
-            if (st.mark.load(w) == v + 1) return ANS_E_SYMBOL;
-            st.mark.store(w, v + 1);
-        }
-    // Prefix::from_full: position p holds input node p, every node known (graph/mod.rs:97-99);
-    // WLOrbitCodecs::apply (incomplete.rs:193-210): a class per degree in the whole graph
-    st.cnt.nsym = orbits == ANS_ORBITS_DEGREE ? nranks : 1;
-    if (orbits != ANS_ORBITS_NONE) st.cnt.clear();
-    for (uint32_t v = 0; v < n; ++v) {
-        st.pos_of.store(v, v);
-        st.node_at.store(v, v);
-        st.mark.store(v, 0);
-        if (orbits != ANS_ORBITS_NONE) {
-            const uint32_t r = class_rank(orbits, rank, st.off.load(v + 1) - st.off.load(v));
-            st.rk.store(v, r);
-            st.cnt.tally(r);
-        }
-    }
-    if (orbits != ANS_ORBITS_NONE) st.cnt.build();
-    for (uint32_t L = n; L > 0; --L) {
-        const uint32_t last = L - 1;
-        if (orbits != ANS_ORBITS_NONE) {
-            // orbit_codec.pop_element (recursive/mod.rs:123): the blanket pop under norm L, then the
-            // class's smallest position (prefix_orbit.rs:117-119), by a scan
-            uint64_t q = 0, cf = 0;
-            if (!c.pop_begin(L, q, cf)) return c.err;
-            const mset::Found f = st.cnt.find(cf);
-            c.pop_end(f.count, q, cf - f.cum);
-            uint32_t index = 0;
-            while (index < last && st.rk.load(index) != f.rank) ++index;
-            // x.swap(index, last_index) (graph.rs:304-331: the two nodes change labels)
-            const uint32_t a = st.node_at.load(index), z = st.node_at.load(last);
-            st.node_at.store(index, z);
-            st.node_at.store(last, a);
-            st.pos_of.store(z, index);
-            st.pos_of.store(a, last);
-            st.rk.store(index, st.rk.load(last));
-            st.cnt.add(f.rank, -1);  // pop_id (prefix_orbit.rs:59-70)
-        }
-        // pop_slice (graph/mod.rs:57-66): the node's edges to positions >= L - 1
-        const uint32_t u = st.node_at.load(last);
-        for (uint32_t a = st.off.load(u), end = st.off.load(u + 1); a < end; ++a) {
-            const uint32_t p = st.pos_of.load(st.nbr.load(a));
-            if (p >= last) st.mark.store(p, L);
-        }
-        // IID<Bernoulli>::push over (L-1, L) .. (L-1, n-1), then the loop: last entry first
-        if (loops) push_bit(c, b, st.mark.load(last) == L);
-        for (uint32_t j = n; j-- > L;) push_bit(c, b, st.mark.load(j) == L);
-        if (c.err) return c.err;
-    }
-    if (perm)
-        for (uint32_t p = 0; p < n; ++p) perm[p] = st.node_at.load(p);
-    return ANS_OK;
-}
-
-// ---- pop.  out receives the pairs (position, position) in pop order, at most cap of them
-// (ANS_E_LEN beyond); *count their number.
-template <class M, class Acc, class Rank>
-ANS_MSET_HD int pop_graph(polya::Coder<M>& c, PopState<Acc>& st, const Bern& b, uint32_t n, bool loops, int orbits,
-                          const Rank& rank, uint32_t nranks, uint32_t* out, uint64_t cap, uint64_t* count) {
-    uint64_t E = 0;
-    *count = 0;
-    st.cnt.nsym = orbits == ANS_ORBITS_DEGREE ? nranks : 1;
-    if (orbits != ANS_ORBITS_NONE) st.cnt.clear();
-    for (uint32_t v = 0; v < n; ++v) st.deg.store(v, 0);
-    for (uint32_t v = 0; v < n; ++v) {
-        uint32_t d = st.deg.load(v);
+    ANS_MSET_HD void start_pop(uint32_t, bool) {}
+    // ... and its pop: the pairs in pop order, the loop last
+    template <class M, class F>
+    ANS_MSET_HD int pop(polya::Coder<M>& c, uint32_t n, bool loops, uint32_t v, uint64_t room, uint32_t& len, F&& emit) {
         for (uint32_t j = v + 1; j < n + (loops ? 1u : 0u); ++j) {
-            const uint32_t w = j < n ? j : v;  // the loop comes last
-            const uint32_t x = pop_bit(c, b);
+            const uint32_t x = pop_bit(c, bern);
             if (c.err) return c.err;
             if (!x) continue;
-            if (E >= cap) return ANS_E_LEN;
-            out[2 * E] = v;
-            out[2 * E + 1] = w;
-            ++E;
-            ++d;
-            if (w != v) st.deg.store(w, st.deg.load(w) + 1);
+            if (len >= room) return ANS_E_LEN;
+            emit(j < n ? j : v);
+            ++len;
         }
-        if (orbits != ANS_ORBITS_NONE) {
-            // push_id, update_around_slice, push_element (recursive/mod.rs:143-145)
-            const uint32_t r = class_rank(orbits, rank, d);
-            st.cnt.add(r, 1);
-            c.push(st.cnt.count(r), uint64_t(v) + 1, st.cnt.prefix(r));
-            if (c.err) return c.err;
-        }
+        return ANS_OK;
     }
-    *count = E;
-    return ANS_OK;
+};
+
+// ---- the orbit stage at wl_iter = 0 as counts per class (WLOrbitCodecs::apply, incomplete.rs:
+// 193-210): `orbits` says which classes (ANS_ORBITS_NONE: nothing is coded, the labelled codec;
+// ONE_CLASS: every known node has id h0, incomplete.rs:193-196 without the half iteration; DEGREE: a
+// class per degree).  rank: build_degree_ranks of some max_nodes >= n, nranks = max_nodes + 1 its
+// entries (DEGREE alone reads it; the counts span its ranks, one rank otherwise).  The kernels give
+// `orbits` as a constant, so a step carries no test of it.
+//   rk    the class rank of the node at a position;  cnt the orbit counts per rank (a Fenwick tree)
+template <class Acc, class Rank>
+struct CountPush {
+    Acc rk;
+    mset::Counts<Acc> cnt;
+    int orbits;
+    Rank rank;
+    uint32_t nranks;
+    template <class T>
+    ANS_MSET_HD static CountPush make(T& take, uint64_t max_nodes, uint64_t, int orbits, Rank rank, uint32_t nranks) {
+        CountPush o{take(max_nodes), {take(max_nodes + 1), 0}, orbits, rank, nranks};
+        return o;
+    }
+    ANS_MSET_HD bool coded() const { return orbits != ANS_ORBITS_NONE; }
+    ANS_MSET_HD uint32_t class_rank(uint32_t degree) const { return orbits == ANS_ORBITS_DEGREE ? rank[degree] : 0; }
+    template <class G>
+    ANS_MSET_HD void apply_full(const G& g, uint32_t n) {
+        if (!coded()) return;
+        cnt.nsym = orbits == ANS_ORBITS_DEGREE ? nranks : 1;
+        cnt.clear();
+        for (uint32_t v = 0; v < n; ++v) {
+            const uint32_t r = class_rank(g.degree(v));
+            rk.store(v, r);
+            cnt.tally(r);
+        }
+        cnt.build();
+    }
+    // the blanket pop under norm L, then the class's smallest position (prefix_orbit.rs:117-119), by
+    // a scan
+    template <class M>
+    ANS_MSET_HD int pop_element(polya::Coder<M>& c, uint32_t L, uint32_t& index, uint32_t& cls) {
+        uint64_t q = 0, cf = 0;
+        if (!c.pop_begin(L, q, cf)) return c.err;
+        const mset::Found f = cnt.find(cf);
+        c.pop_end(f.count, q, cf - f.cum);
+        cls = f.rank;
+        for (index = 0; index < L - 1 && rk.load(index) != cls;) ++index;
+        return ANS_OK;
+    }
+    // the orbits' swap of the positions index and last, then pop_id (prefix_orbit.rs:59-70)
+    ANS_MSET_HD void pop_id(uint32_t index, uint32_t last, uint32_t cls) {
+        rk.store(index, rk.load(last));
+        cnt.add(cls, -1);
+    }
+    // a class is a degree in the whole graph: a slice that leaves changes none
+    ANS_MSET_HD void touch(uint32_t) {}
+    template <class G>
+    ANS_MSET_HD void after_pop_slice(const G&, uint32_t) {}
+};
+//   deg   the degree so far per position
+template <class Acc, class Rank>
+struct CountPop {
+    Acc deg;
+    mset::Counts<Acc> cnt;
+    int orbits;
+    Rank rank;
+    uint32_t nranks;
+    template <class T>
+    ANS_MSET_HD static CountPop make(T& take, uint64_t max_nodes, uint64_t, int orbits, Rank rank, uint32_t nranks) {
+        CountPop o{take(max_nodes), {take(max_nodes + 1), 0}, orbits, rank, nranks};
+        return o;
+    }
+    ANS_MSET_HD void start_pop(uint32_t n, const uint32_t*) {
+        if (orbits == ANS_ORBITS_NONE) return;
+        cnt.nsym = orbits == ANS_ORBITS_DEGREE ? nranks : 1;
+        cnt.clear();
+        for (uint32_t v = 0; v < n; ++v) deg.store(v, 0);
+    }
+    ANS_MSET_HD void add_pair(uint32_t v, uint32_t w, uint32_t) {
+        if (orbits != ANS_ORBITS_NONE && w != v) deg.store(w, deg.load(w) + 1);
+    }
+    // push_id, update_around_slice, push_element (recursive/mod.rs:143-145): v's slice held len pairs
+    template <class M>
+    ANS_MSET_HD int push_element(polya::Coder<M>& c, uint32_t v, uint32_t len) {
+        if (orbits == ANS_ORBITS_NONE) return ANS_OK;
+        const uint32_t r = orbits == ANS_ORBITS_DEGREE ? rank[deg.load(v) + len] : 0;
+        cnt.add(r, 1);
+        c.push(cnt.count(r), uint64_t(v) + 1, cnt.prefix(r));
+        return c.err;
+    }
+};
+constexpr uint64_t count_entries(uint64_t max_nodes) { return 2 * max_nodes + 1; }
+
+// The per-graph states (ans_rgraph.hpp lays them out): the prefix graph, the stamps, the counts; a
+// pop holds nothing sized by the edges.
+constexpr uint64_t push_entries(uint64_t max_nodes, uint64_t max_edges) {
+    return rgraph::graph_entries(max_nodes, max_edges) + max_nodes + count_entries(max_nodes);
 }
+constexpr uint64_t pop_entries(uint64_t max_nodes) { return count_entries(max_nodes); }
+template <class Acc, class Rank>
+using PushState = rgraph::PushState<Acc, ErSlices<Acc>, CountPush<Acc, Rank>>;
+template <class Acc, class Rank>
+using PopState = rgraph::PopState<Acc, ErSlices<Acc>, CountPop<Acc, Rank>>;
 
 // Bytes a message can grow by during a push or a pop of a graph of at most max_nodes nodes
 // (ans_gpu_ar_er_slack; DESIGN.md §3.10 derives it): a push adds n(n-1)/2 + n*loops indicators of

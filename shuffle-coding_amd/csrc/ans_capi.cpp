@@ -348,30 +348,87 @@ int ans_polya_pop(ans_msg* m, uint32_t num_nodes, int loops, int redraws, uint32
     });
 }
 
-// ---- the autoregressive Erdős–Rényi graph codecs on one message (ans_arer.hpp):
-// Autoregressive(ErdosRenyiSliceCodecs) and ShuffleCodec<.., WLOrbitCodecs> with wl_iter = 0,
-// src/recursive/mod.rs:117-216, src/recursive/graph/slice.rs:16-59, incomplete.rs:189-236
+// ---- recursive shuffle coding of a graph on one message (ans_rgraph.hpp): the autoregressive
+// Erdős–Rényi (ans_arer.hpp) and Pólya urn (ans_arpu.hpp) slices, as a labelled graph or under the
+// orbits of wl_iter = 0 as counts per class (Autoregressive(..) and ShuffleCodec<.., WLOrbitCodecs>,
+// src/recursive/mod.rs:117-216, src/recursive/graph/slice.rs, incomplete.rs:189-236), or with
+// Weisfeiler-Lehman orbits at wl_iter <= ANS_WL_MAX_ITER (ans_wl.hpp: incomplete.rs:45-57, 87-151)
 extern "C++" {
 namespace {
-struct SizedWs {  // ans_arer.hpp's states name each array's length; a vector needs only its start
+struct SizedWs {  // the states name each array's length; a vector needs only its start
     uint32_t* p;
     VecAcc at(uint64_t o, uint64_t) const { return VecAcc{p + o}; }
 };
-template <class F>
-int arer_host(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int orbits, F&& f) {
-    return guarded([&] {
-        if (bern->cat.masses.size() != 2) throw AnsError(ANS_E_ARG, "the indicator table needs exactly two symbols");
+// an orbit stage's setting: checked, then what the state's make takes after the bounds
+struct CountSetting {
+    int orbits;
+    std::vector<uint32_t> rank;
+    void check(uint32_t num_nodes) {
         if (orbits != ANS_ORBITS_NONE && orbits != ANS_ORBITS_ONE_CLASS && orbits != ANS_ORBITS_DEGREE)
             throw AnsError(ANS_E_ARG, "orbits outside NONE, ONE_CLASS, DEGREE");
         if (num_nodes > 0x7FFFFFFFu) throw AnsError(ANS_E_ARG, "2^31 or more nodes");
-        std::vector<uint32_t> rank;
         if (orbits == ANS_ORBITS_DEGREE && !arer::build_degree_ranks(num_nodes, rank))
             throw AnsError(ANS_E_ARG, "two degrees share a class id");
-        const arer::Bern b = arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]);
+    }
+    template <class St>
+    St make(const SizedWs& ws, uint32_t num_nodes, uint64_t max_edges) const {
+        return St::make(ws, num_nodes, max_edges, orbits, static_cast<const uint32_t*>(rank.data()), num_nodes + 1);
+    }
+};
+struct WlSetting {
+    int wl_iter, half_iter;
+    void check(uint32_t num_nodes) const {
+        if (wl_iter < 0 || wl_iter > ANS_WL_MAX_ITER) throw AnsError(ANS_E_ARG, "wl_iter outside 0 .. ANS_WL_MAX_ITER");
+        if (!wl::nodes_ok(num_nodes, wl_iter)) throw AnsError(ANS_E_ARG, "2^31 or more nodes, or 2^32 or more id words");
+    }
+    template <class St>
+    St make(const SizedWs& ws, uint32_t num_nodes, uint64_t max_edges) const {
+        return St::make(ws, num_nodes, max_edges, static_cast<uint32_t>(wl_iter), half_iter != 0);
+    }
+};
+void set_bern(arer::ErSlices<VecAcc>& s, const ans_table* bern) {
+    s.bern = arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]);
+}
+void set_bern(arpu::PuSlices<VecAcc>&, const ans_table*) {}
+
+using CountRank = const uint32_t*;
+// St over a vector of `entries`, bounded by num_nodes and max_edges; run(coder, state) is the codec.
+// bern: the table of the Erdős–Rényi slices, null for the Pólya urn's.
+template <class St, class Setting, class Run>
+int graph_host(ans_msg* m, const ans_table* bern, Setting setting, uint64_t entries, uint32_t num_nodes, uint64_t max_edges,
+               Run&& run) {
+    return guarded([&] {
+        if (bern && bern->cat.masses.size() != 2) throw AnsError(ANS_E_ARG, "the indicator table needs exactly two symbols");
+        setting.check(num_nodes);
+        std::vector<uint32_t> ws(entries);
+        St st = setting.template make<St>(SizedWs{ws.data()}, num_nodes, max_edges);
+        set_bern(st, bern);
         HostMsg hm{m->m, m->m.head};
         polya::Coder<HostMsg> c{hm, ANS_OK};
-        if (const int rc = f(c, b, rank.data())) throw AnsError(rc, ans_status_string(rc));
+        if (const int rc = run(c, st)) throw AnsError(rc, ans_status_string(rc));
     });
+}
+template <class St, class Setting>
+int graph_push(ans_msg* m, const ans_table* bern, Setting setting, uint64_t entries, uint32_t num_nodes, int loops,
+               const uint32_t* edges, size_t num_edges, uint32_t* perm) {
+    return graph_host<St>(m, bern, std::move(setting), entries, num_nodes, num_edges, [&](auto& c, St& st) {
+        return rgraph::push_graph(c, st, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
+    });
+}
+// room: the pairs the state is bounded by; at most cap of them come out
+template <class St, class Setting>
+int graph_pop(ans_msg* m, const ans_table* bern, Setting setting, uint64_t entries, uint32_t num_nodes, uint64_t room,
+              int loops, uint32_t* edges, uint64_t cap, size_t* num_edges) {
+    return graph_host<St>(m, bern, std::move(setting), entries, num_nodes, room, [&](auto& c, St& st) {
+        uint64_t count = 0;
+        const int rc = rgraph::pop_graph(c, st, num_nodes, loops != 0, edges, cap, &count);
+        *num_edges = static_cast<size_t>(count);
+        return rc;
+    });
+}
+// (no graph holds more pairs than its alphabet: a larger cap sizes nothing)
+uint64_t pop_room(uint32_t num_nodes, size_t cap) {
+    return std::min<uint64_t>({cap, uint64_t(num_nodes) * (num_nodes + 1) / 2, rgraph::kMaxEdges});
 }
 }  // namespace
 }  // extern "C++" (templates)
@@ -379,143 +436,67 @@ int arer_host(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int orbits,
 int ans_ar_er_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int orbits, const uint32_t* edges,
                    size_t num_edges, uint32_t* perm) {
     if (!m || !bern || (num_edges && !edges) || num_edges > arer::kMaxEdges) return ANS_E_ARG;
-    return arer_host(m, bern, num_nodes, orbits, [&](auto& c, const arer::Bern& b, const uint32_t* rank) {
-        std::vector<uint32_t> ws(arer::push_entries(num_nodes, num_edges));
-        auto st = arer::PushState<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges);
-        return arer::push_graph(c, st, b, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, static_cast<uint32_t>(num_edges),
-                                perm);
-    });
+    return graph_push<arer::PushState<VecAcc, CountRank>>(m, bern, CountSetting{orbits, {}},
+                                                          arer::push_entries(num_nodes, num_edges), num_nodes, loops, edges,
+                                                          num_edges, perm);
 }
 
 int ans_ar_er_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int orbits, uint32_t* edges,
                   size_t cap, size_t* num_edges) {
     if (!m || !bern || !num_edges || (cap && !edges)) return ANS_E_ARG;
     *num_edges = 0;
-    return arer_host(m, bern, num_nodes, orbits, [&](auto& c, const arer::Bern& b, const uint32_t* rank) {
-        std::vector<uint32_t> ws(arer::pop_entries(num_nodes));
-        auto st = arer::PopState<VecAcc>::make(SizedWs{ws.data()}, num_nodes);
-        uint64_t count = 0;
-        const int rc = arer::pop_graph(c, st, b, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, cap, &count);
-        *num_edges = static_cast<size_t>(count);
-        return rc;
-    });
+    return graph_pop<arer::PopState<VecAcc, CountRank>>(m, bern, CountSetting{orbits, {}}, arer::pop_entries(num_nodes),
+                                                        num_nodes, 0, loops, edges, cap, num_edges);
 }
-
-// ---- the autoregressive Pólya urn graph codecs on one message (ans_arpu.hpp):
-// Autoregressive(PolyaUrnSliceCodecs) and ShuffleCodec<.., WLOrbitCodecs> with wl_iter = 0,
-// src/recursive/mod.rs:117-216, src/recursive/graph/slice.rs:61-230, incomplete.rs:189-236
-extern "C++" {
-namespace {
-template <class F>
-int arpu_host(ans_msg* m, uint32_t num_nodes, int orbits, F&& f) {
-    return guarded([&] {
-        if (orbits != ANS_ORBITS_NONE && orbits != ANS_ORBITS_ONE_CLASS && orbits != ANS_ORBITS_DEGREE)
-            throw AnsError(ANS_E_ARG, "orbits outside NONE, ONE_CLASS, DEGREE");
-        if (num_nodes > 0x7FFFFFFFu) throw AnsError(ANS_E_ARG, "2^31 or more nodes");
-        std::vector<uint32_t> rank;
-        if (orbits == ANS_ORBITS_DEGREE && !arer::build_degree_ranks(num_nodes, rank))
-            throw AnsError(ANS_E_ARG, "two degrees share a class id");
-        HostMsg hm{m->m, m->m.head};
-        polya::Coder<HostMsg> c{hm, ANS_OK};
-        if (const int rc = f(c, rank.data())) throw AnsError(rc, ans_status_string(rc));
-    });
-}
-}  // namespace
-}  // extern "C++" (templates)
 
 int ans_ar_polya_push(ans_msg* m, uint32_t num_nodes, int loops, int orbits, const uint32_t* edges, size_t num_edges,
                       uint32_t* perm) {
     if (!m || (num_edges && !edges) || num_edges > arpu::kMaxEdges) return ANS_E_ARG;
-    return arpu_host(m, num_nodes, orbits, [&](auto& c, const uint32_t* rank) {
-        std::vector<uint32_t> ws(arpu::push_entries(num_nodes, num_edges));
-        auto st = arpu::PushState<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges);
-        return arpu::push_graph(c, st, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges,
-                                static_cast<uint32_t>(num_edges), perm);
-    });
+    return graph_push<arpu::PushState<VecAcc, CountRank>>(m, nullptr, CountSetting{orbits, {}},
+                                                          arpu::push_entries(num_nodes, num_edges), num_nodes, loops, edges,
+                                                          num_edges, perm);
 }
 
 int ans_ar_polya_pop(ans_msg* m, uint32_t num_nodes, int loops, int orbits, uint32_t* edges, size_t cap,
                      size_t* num_edges) {
     if (!m || !num_edges || (cap && !edges)) return ANS_E_ARG;
     *num_edges = 0;
-    return arpu_host(m, num_nodes, orbits, [&](auto& c, const uint32_t* rank) {
-        std::vector<uint32_t> ws(arpu::pop_entries(num_nodes));
-        auto st = arpu::PopState<VecAcc>::make(SizedWs{ws.data()}, num_nodes);
-        uint64_t count = 0;
-        const int rc = arpu::pop_graph(c, st, num_nodes, loops != 0, orbits, rank, num_nodes + 1, edges, cap, &count);
-        *num_edges = static_cast<size_t>(count);
-        return rc;
-    });
+    return graph_pop<arpu::PopState<VecAcc, CountRank>>(m, nullptr, CountSetting{orbits, {}}, arpu::pop_entries(num_nodes),
+                                                        num_nodes, 0, loops, edges, cap, num_edges);
 }
-
-// ---- the same with Weisfeiler-Lehman orbits at wl_iter <= ANS_WL_MAX_ITER (ans_wl.hpp):
-// incomplete.rs:45-57, 87-151, 189-236
-extern "C++" {
-namespace {
-template <class F>
-int wl_host(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int wl_iter, F&& f) {
-    return guarded([&] {
-        if (bern && bern->cat.masses.size() != 2) throw AnsError(ANS_E_ARG, "the indicator table needs exactly two symbols");
-        if (wl_iter < 0 || wl_iter > ANS_WL_MAX_ITER) throw AnsError(ANS_E_ARG, "wl_iter outside 0 .. ANS_WL_MAX_ITER");
-        if (!wl::nodes_ok(num_nodes, wl_iter)) throw AnsError(ANS_E_ARG, "2^31 or more nodes, or 2^32 or more id words");
-        const arer::Bern b = bern ? arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]) : arer::Bern{};
-        HostMsg hm{m->m, m->m.head};
-        polya::Coder<HostMsg> c{hm, ANS_OK};
-        if (const int rc = f(c, b)) throw AnsError(rc, ans_status_string(rc));
-    });
-}
-}  // namespace
-}  // extern "C++" (templates)
 
 int ans_ar_er_wl_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
                       const uint32_t* edges, size_t num_edges, uint32_t* perm) {
     if (!m || !bern || (num_edges && !edges) || num_edges > arer::kMaxEdges) return ANS_E_ARG;
-    return wl_host(m, bern, num_nodes, wl_iter, [&](auto& c, const arer::Bern& b) {
-        std::vector<uint32_t> ws(wl::er_push_entries(num_nodes, num_edges, wl_iter));
-        auto st = wl::ErPush<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges, wl_iter, half_iter != 0);
-        return wl::er_push_graph(c, st, b, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
-    });
+    return graph_push<wl::ErPush<VecAcc>>(m, bern, WlSetting{wl_iter, half_iter},
+                                          wl::er_push_entries(num_nodes, num_edges, wl_iter), num_nodes, loops, edges,
+                                          num_edges, perm);
 }
 
 int ans_ar_er_wl_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
                      uint32_t* edges, size_t cap, size_t* num_edges) {
     if (!m || !bern || !num_edges || (cap && !edges)) return ANS_E_ARG;
     *num_edges = 0;
-    // (no graph holds more pairs than its alphabet: a larger cap sizes nothing)
-    const uint64_t all = uint64_t(num_nodes) * (num_nodes + 1) / 2, room = std::min<uint64_t>({cap, all, arer::kMaxEdges});
-    return wl_host(m, bern, num_nodes, wl_iter, [&](auto& c, const arer::Bern& b) {
-        std::vector<uint32_t> ws(wl::er_pop_entries(num_nodes, room, wl_iter));
-        auto st = wl::ErPop<VecAcc>::make(SizedWs{ws.data()}, num_nodes, room, wl_iter, half_iter != 0);
-        uint64_t count = 0;
-        const int rc = wl::er_pop_graph(c, st, b, num_nodes, loops != 0, edges, room, &count);
-        *num_edges = static_cast<size_t>(count);
-        return rc;
-    });
+    const uint64_t room = pop_room(num_nodes, cap);
+    return graph_pop<wl::ErPop<VecAcc>>(m, bern, WlSetting{wl_iter, half_iter}, wl::er_pop_entries(num_nodes, room, wl_iter),
+                                        num_nodes, room, loops, edges, room, num_edges);
 }
 
 int ans_ar_polya_wl_push(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, const uint32_t* edges,
                          size_t num_edges, uint32_t* perm) {
     if (!m || (num_edges && !edges) || num_edges > arpu::kMaxEdges) return ANS_E_ARG;
-    return wl_host(m, nullptr, num_nodes, wl_iter, [&](auto& c, const arer::Bern&) {
-        std::vector<uint32_t> ws(wl::pu_push_entries(num_nodes, num_edges, wl_iter));
-        auto st = wl::PuPush<VecAcc>::make(SizedWs{ws.data()}, num_nodes, num_edges, wl_iter, half_iter != 0);
-        return wl::pu_push_graph(c, st, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
-    });
+    return graph_push<wl::PuPush<VecAcc>>(m, nullptr, WlSetting{wl_iter, half_iter},
+                                          wl::pu_push_entries(num_nodes, num_edges, wl_iter), num_nodes, loops, edges,
+                                          num_edges, perm);
 }
 
 int ans_ar_polya_wl_pop(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, uint32_t* edges,
                         size_t cap, size_t* num_edges) {
     if (!m || !num_edges || (cap && !edges)) return ANS_E_ARG;
     *num_edges = 0;
-    const uint64_t all = uint64_t(num_nodes) * (num_nodes + 1) / 2, room = std::min<uint64_t>({cap, all, arpu::kMaxEdges});
-    return wl_host(m, nullptr, num_nodes, wl_iter, [&](auto& c, const arer::Bern&) {
-        std::vector<uint32_t> ws(wl::pu_pop_entries(num_nodes, room, wl_iter));
-        auto st = wl::PuPop<VecAcc>::make(SizedWs{ws.data()}, num_nodes, room, wl_iter, half_iter != 0);
-        uint64_t count = 0;
-        const int rc = wl::pu_pop_graph(c, st, num_nodes, loops != 0, edges, room, &count);
-        *num_edges = static_cast<size_t>(count);
-        return rc;
-    });
+    const uint64_t room = pop_room(num_nodes, cap);
+    return graph_pop<wl::PuPop<VecAcc>>(m, nullptr, WlSetting{wl_iter, half_iter}, wl::pu_pop_entries(num_nodes, room, wl_iter),
+                                        num_nodes, room, loops, edges, room, num_edges);
 }
 
 }  // extern "C"

@@ -1,251 +1,72 @@
-// The per-graph states of the autoregressive Erdős–Rényi codecs (ans_arer.hpp PushState, PopState)
-// behind a checked accessor: one workspace of fixed bounds reused for every graph, full of junk
-// before every push and every pop, as a lane's entries of the device workspace are.  The shared
-// templates (PushState, PopState, push_graph, pop_graph: the functions the kernels of ans_arer.hip
-// and the host codec run) are instantiated with
-//   * an accessor that knows its region of the workspace (Ws::at names its start and its length)
-//     and counts every access at or past the region's end (not performed: the load gives kOobValue,
-//     the store is dropped) and every load of an entry that the current call has not stored (a stale
-//     read: on the device another graph's leftovers);
-//   * a rank table that counts a read past its max_nodes + 1 entries;
-//   * a message that is a head and a byte vector, with the renorm of src/ans.rs:233-253 under the
-//     Empty generator.
-// Built with ASan + UBSan and run by tests/test_arer_state.py, which parses the summary line.
-// --short declares every region one entry shorter than it is: the run must then report accesses
-// out of range (the check of the checker).  Those entries exist, so in that run an access to one
-// is counted and performed all the same, and the codec's results still hold.
-#include <algorithm>
-#include <array>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <random>
-#include <utility>
-#include <vector>
-
+// The per-graph states of the autoregressive Erdős–Rényi codecs (ans_arer.hpp PushState, PopState:
+// the recursion of ans_rgraph.hpp over ErSlices and the counts per class) behind the checked accessor
+// of state_check.hpp, under each orbits value.  Run by tests/test_arer_state.py.
 #include "ans_arer.hpp"
+#include "state_check.hpp"
 
 namespace ar = shuffle_coding::arer;
-namespace pu = shuffle_coding::polya;
+namespace rg = shuffle_coding::rgraph;
+using namespace state_check;
+using Coder = shuffle_coding::polya::Coder<Msg>;
 
 namespace {
 
 constexpr uint32_t kMaxNodes = 40, kMaxEdges = 200;
-constexpr int kPushRegions = 7, kRegions = 9;  // push's, then pop's over the same entries
-const char* const kRegionName[kRegions] = {"pos_of", "node_at", "off", "nbr", "mark", "rk", "cnt", "deg", "pop_cnt"};
-constexpr uint32_t kOobValue = 0;  // what a load out of range gives (a value every caller survives)
+constexpr int kPushRegions = 7;  // push's, then pop's over the same entries
+const char* const kRegionName[] = {"pos_of", "node_at", "off", "nbr", "mark", "rk", "cnt", "deg", "pop_cnt"};
 
-struct Shadow {
-    std::vector<uint32_t> value, stamp;
-    uint32_t epoch = 0;
-    std::array<uint64_t, kRegions> begin{}, end{}, declared_end{}, oob{}, stale{};
-    std::array<int64_t, kRegions> highest;
-    int regions = 0;
-    uint64_t rank_oob = 0;
-    Shadow() { highest.fill(-1); }
-};
-
-struct CheckedAcc {
-    Shadow* s;
-    int region;
-    bool in_range(uint32_t i) const {
-        const uint64_t at = s->begin[region] + i;
-        if (at >= s->declared_end[region]) ++s->oob[region];
-        if (at >= s->end[region]) return false;
-        s->highest[region] = std::max<int64_t>(s->highest[region], i);
-        return true;
-    }
-    uint32_t load(uint32_t i) const {
-        if (!in_range(i)) return kOobValue;
-        const uint64_t at = s->begin[region] + i;
-        if (s->stamp[at] != s->epoch) ++s->stale[region];
-        return s->value[at];
-    }
-    void store(uint32_t i, uint32_t v) {
-        if (!in_range(i)) return;
-        const uint64_t at = s->begin[region] + i;
-        s->value[at] = v;
-        s->stamp[at] = s->epoch;
-    }
-};
-struct CheckedWs {
-    Shadow* s;
-    CheckedAcc at(uint64_t o, uint64_t count) const {
-        const int r = s->regions++;
-        s->begin[r] = o;
-        s->end[r] = o + count;
-        return CheckedAcc{s, r};
-    }
-};
-struct CheckedRank {
-    const uint32_t* p;
-    uint32_t entries;
-    Shadow* s;
-    uint32_t operator[](uint32_t d) const {
-        if (d < entries) return p[d];
-        ++s->rank_oob;
-        return 0;
-    }
-};
-
-// Message::unflatten(bytes) with the Empty generator: head 0, the bytes as the tail
-struct Msg {
-    uint64_t head = 0;
-    std::vector<uint8_t> tail;
-    bool renorm(uint64_t min_head) {
-        while (head < min_head) {
-            if (tail.empty()) return false;  // src/ans.rs:144
-            head = (head << 8) | tail.back();
-            tail.pop_back();
-        }
-        while ((head >> 8) >= min_head) {
-            tail.push_back(static_cast<uint8_t>(head));
-            head >>= 8;
-        }
-        return true;
-    }
-    std::vector<uint8_t> flatten() const {  // src/ans.rs:255-260
-        std::vector<uint8_t> b = tail;
-        uint64_t h = head;
-        while ((h >> 8) >= 1) {
-            b.push_back(static_cast<uint8_t>(h));
-            h >>= 8;
-        }
-        b.push_back(static_cast<uint8_t>(h));
-        return b;
-    }
-};
-
-using Pairs = std::vector<std::pair<uint32_t, uint32_t>>;
-
-struct Checker {
-    std::mt19937_64 rng{20261021};
-    Shadow sh;
+struct Checker : Common {
     std::vector<uint32_t> rank;
-    ar::PushState<CheckedAcc> push;
-    ar::PopState<CheckedAcc> pop;
-    const ar::Bern bern = ar::bern_of(900, 100);
-    uint64_t graphs = 0, roundtrip_fail = 0, hostile = 0, hostile_ok = 0, hostile_bad = 0, exhausted = 0, len = 0;
+    ar::PushState<CheckedAcc, CheckedRank> push;
+    ar::PopState<CheckedAcc, CheckedRank> pop;
 
     explicit Checker(bool shorter) : push(make_push()), pop(make_pop(shorter)) {}
-    ar::PushState<CheckedAcc> make_push() {
-        const uint64_t entries = ar::push_entries(kMaxNodes, kMaxEdges);
-        sh.value.assign(entries, 0);
-        sh.stamp.assign(entries, 0);
+    CheckedRank ranks() { return CheckedRank{rank.data(), kMaxNodes + 1, &sh}; }
+    ar::PushState<CheckedAcc, CheckedRank> make_push() {
+        sh.resize(ar::push_entries(kMaxNodes, kMaxEdges));
         if (!ar::build_degree_ranks(kMaxNodes, rank)) std::exit(2);
-        return ar::PushState<CheckedAcc>::make(CheckedWs{&sh}, kMaxNodes, kMaxEdges);
-    }
-    ar::PopState<CheckedAcc> make_pop(bool shorter) {
-        auto state = ar::PopState<CheckedAcc>::make(CheckedWs{&sh}, kMaxNodes);
-        if (sh.regions != kRegions || sh.end[kPushRegions - 1] != sh.value.size() ||
-            sh.end[kRegions - 1] != ar::pop_entries(kMaxNodes))
-            std::exit(2);
-        sh.declared_end = sh.end;
-        if (shorter)
-            for (auto& e : sh.declared_end) --e;
+        auto state = ar::PushState<CheckedAcc, CheckedRank>::make(CheckedWs{&sh}, kMaxNodes, kMaxEdges, 0, ranks(), kMaxNodes + 1);
+        state.bern = ar::bern_of(900, 100);
         return state;
     }
-    // what a lane finds: every entry holds something, none of it this call's
-    void fresh() {
-        ++sh.epoch;
-        for (auto& v : sh.value) v = static_cast<uint32_t>(rng());
+    ar::PopState<CheckedAcc, CheckedRank> make_pop(bool shorter) {
+        auto state = ar::PopState<CheckedAcc, CheckedRank>::make(CheckedWs{&sh}, kMaxNodes, 0, 0, ranks(), kMaxNodes + 1);
+        state.bern = ar::bern_of(900, 100);
+        if (sh.regions[kPushRegions - 1].end != sh.value.size() || sh.regions.back().end != ar::pop_entries(kMaxNodes))
+            std::exit(2);
+        if (shorter) sh.shorten();
+        return state;
     }
-    uint64_t below(uint64_t n) { return rng() % n; }
-    CheckedRank ranks() { return CheckedRank{rank.data(), kMaxNodes + 1, &sh}; }
-
-    Pairs alphabet(uint32_t n, bool loops) {
-        Pairs all;
-        for (uint32_t j = 0; j < n; ++j)
-            for (uint32_t i = 0; i < (loops ? j + 1 : j); ++i) all.emplace_back(i, j);
-        return all;
-    }
-    Pairs random_graph(uint32_t n, uint32_t want, bool loops) {
-        Pairs all = alphabet(n, loops);
-        const size_t E = std::min<size_t>(want, all.size());
-        for (size_t k = 0; k < E; ++k) std::swap(all[k], all[k + below(all.size() - k)]);
-        all.resize(E);
-        return all;
+    auto popper(uint32_t n, bool loops, int orbits) {
+        pop.orb.orbits = orbits;
+        return [this, n, loops](Coder& c, uint32_t* out, uint64_t cap, uint64_t* count) {
+            return rg::pop_graph(c, pop, n, loops, out, cap, count);
+        };
     }
 
-    // push onto the seed, pop from what the push left; the state is junk before either
     void roundtrip(uint32_t n, const Pairs& g, bool loops, int orbits) {
-        const uint32_t E = static_cast<uint32_t>(g.size());
-        std::vector<uint8_t> seed(400);
-        for (auto& b : seed) b = static_cast<uint8_t>(rng());
-        seed.back() |= 1;  // a nonzero top byte: the seed comes back byte for byte
-        std::vector<uint32_t> e(2 * size_t(E) + 2, 0xDEADBEEFu), out(2 * size_t(E) + 2, 0xDEADBEEFu), perm(n + 1, 0xDEADBEEFu);
-        for (uint32_t k = 0; k < E; ++k) {
-            e[2 * k] = g[k].first;
-            e[2 * k + 1] = g[k].second;
+        push.orb.orbits = orbits;
+        const uint64_t steps = orbits != ANS_ORBITS_NONE ? n : uint64_t(n) * (n - (n ? 1 : 0)) / 2 + (loops ? n : 0);
+        int rc = 0;
+        std::vector<uint32_t> perm;
+        if (!Common::roundtrip<Coder>(
+                n, g, steps == 0, false,
+                [&](Coder& c, const uint32_t* e, uint32_t E, uint32_t* p) { return rg::push_graph(c, push, n, loops, e, E, p); },
+                popper(n, loops, orbits), rc, perm)) {
+            ++roundtrip_fail;
+            std::fprintf(stderr, "round trip failed: n=%u E=%zu loops=%d orbits=%d rc=%d\n", n, g.size(), loops, orbits, rc);
         }
-        ++graphs;
-        Msg m;
-        m.tail = seed;
-        pu::Coder<Msg> c{m, ANS_OK};
-        fresh();
-        int rc = ar::push_graph(c, push, bern, n, loops, orbits, ranks(), kMaxNodes + 1, e.data(), E, perm.data());
-        Msg m2;
-        m2.tail = m.flatten();
-        pu::Coder<Msg> c2{m2, ANS_OK};
-        uint64_t count = 0;
-        fresh();
-        if (!rc) rc = ar::pop_graph(c2, pop, bern, n, loops, orbits, ranks(), kMaxNodes + 1, out.data(), E, &count);
-        bool ok = rc == ANS_OK && count == E && perm[n] == 0xDEADBEEFu;
-        if (ok) {
-            std::vector<uint32_t> pos(n);
-            for (uint32_t p = 0; p < n; ++p) {
-                if (perm[p] >= n) return fail(n, E, loops, orbits, rc);
-                pos[perm[p]] = p;
-            }
-            Pairs want, got;
-            for (auto& [i, j] : g) want.emplace_back(std::min(pos[i], pos[j]), std::max(pos[i], pos[j]));
-            for (uint32_t k = 0; k < E; ++k) got.emplace_back(out[2 * k], out[2 * k + 1]);
-            std::sort(want.begin(), want.end());
-            std::sort(got.begin(), got.end());
-            std::vector<uint8_t> rest = seed;
-            // without a step each call is flatten(unflatten(B)) = B ++ [0]
-            const uint64_t steps = orbits != ANS_ORBITS_NONE ? n : uint64_t(n) * (n - (n ? 1 : 0)) / 2 + (loops ? n : 0);
-            if (steps == 0) rest.insert(rest.end(), 2, 0);
-            ok = got == want && m2.flatten() == rest;
-        }
-        if (!ok) fail(n, E, loops, orbits, rc);
-    }
-    void fail(uint32_t n, uint32_t E, bool loops, int orbits, int rc) {
-        ++roundtrip_fail;
-        std::fprintf(stderr, "round trip failed: n=%u E=%u loops=%d orbits=%d rc=%d\n", n, E, loops, orbits, rc);
     }
 
     // bytes no push wrote: a graph of the alphabet, exhaustion, or more pairs than the capacity
     void hostile_pop(bool loops, int orbits) {
         const uint32_t n = static_cast<uint32_t>(below(kMaxNodes + 1));
         const uint64_t cap = below(60);
-        Msg m;
-        m.tail.resize(1 + below(40));
-        for (auto& b : m.tail) b = static_cast<uint8_t>(rng());
-        std::vector<uint32_t> out(2 * cap + 2, 0xDEADBEEFu);
-        pu::Coder<Msg> c{m, ANS_OK};
-        uint64_t count = 0;
-        fresh();
-        const int rc = ar::pop_graph(c, pop, bern, n, loops, orbits, ranks(), kMaxNodes + 1, out.data(), cap, &count);
-        ++hostile;
-        if (out[2 * cap] != 0xDEADBEEFu) ++hostile_bad;
-        switch (rc) {
-        case ANS_OK:
-            ++hostile_ok;
-            for (uint64_t k = 0; k < count; ++k) {
-                const uint32_t i = out[2 * k], j = out[2 * k + 1];
-                if (count > cap || i > j || j >= n || (i == j && !loops)) {
-                    ++hostile_bad;
-                    std::fprintf(stderr, "hostile pop: pair (%u, %u) outside the alphabet, n=%u\n", i, j, n);
-                    break;
-                }
-            }
-            break;
+        switch (const int rc = Common::hostile_pop<Coder>(n, cap, 40, loops, popper(n, loops, orbits))) {
+        case ANS_OK: break;
         case ANS_E_EXHAUSTED: ++exhausted; break;
         case ANS_E_LEN: ++len; break;
-        default:
-            ++hostile_bad;
-            std::fprintf(stderr, "hostile pop: status %d\n", rc);
+        default: bad_status(rc);
         }
     }
 };
@@ -253,8 +74,7 @@ struct Checker {
 }  // namespace
 
 int main(int argc, char** argv) {
-    const bool shorter = argc > 1 && std::strcmp(argv[1], "--short") == 0;
-    Checker ck(shorter);
+    Checker ck(short_run(argc, argv));
     auto run = [&](uint32_t n, const Pairs& g, bool loops, int orbits) {
         ck.roundtrip(n, g, loops, orbits);
         ck.hostile_pop(loops, orbits);
@@ -292,19 +112,18 @@ int main(int argc, char** argv) {
         if (k % 50 == 49) n = kMaxNodes, E = kMaxEdges;
         run(n, ck.random_graph(n, E, loops), loops, static_cast<int>(k % 3));
     }
-    const Shadow& sh = ck.sh;
-    uint64_t oob = 0, stale = 0;
-    for (int r = 0; r < kRegions; ++r) oob += sh.oob[r], stale += sh.stale[r];
-    std::printf("arer_state_check: graphs=%llu named=%llu roundtrip_fail=%llu hostile=%llu hostile_ok=%llu "
-                "exhausted=%llu len=%llu hostile_bad=%llu rank_oob=%llu oob=%llu stale=%llu",
-                (unsigned long long)(ck.graphs - named_graphs), (unsigned long long)named,
-                (unsigned long long)ck.roundtrip_fail, (unsigned long long)ck.hostile, (unsigned long long)ck.hostile_ok,
-                (unsigned long long)ck.exhausted, (unsigned long long)ck.len, (unsigned long long)ck.hostile_bad,
-                (unsigned long long)sh.rank_oob, (unsigned long long)oob, (unsigned long long)stale);
-    for (int r = 0; r < kRegions; ++r)
-        std::printf(" %s:size=%llu,highest=%lld,oob=%llu,stale=%llu", kRegionName[r],
-                    (unsigned long long)(sh.declared_end[r] - sh.begin[r]), (long long)sh.highest[r],
-                    (unsigned long long)sh.oob[r], (unsigned long long)sh.stale[r]);
-    std::printf("\n");
+    std::printf("arer_state_check:");
+    Common::field("graphs", ck.graphs - named_graphs);
+    Common::field("named", named);
+    Common::field("roundtrip_fail", ck.roundtrip_fail);
+    Common::field("hostile", ck.hostile);
+    Common::field("hostile_ok", ck.hostile_ok);
+    Common::field("exhausted", ck.exhausted);
+    Common::field("len", ck.len);
+    Common::field("hostile_bad", ck.hostile_bad);
+    Common::field("rank_oob", ck.sh.rank_oob);
+    Common::field("oob", ck.oob());
+    Common::field("stale", ck.stale());
+    ck.print_regions(kRegionName);
     return 0;
 }

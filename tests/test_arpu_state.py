@@ -15,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLICE = dict(sl=40, ord=40, rop=40, por=40, ids=80, orb=40)  # the slice scratch: 7 * 40
 # max_nodes 40, max_edges 200: push 13 * 40 + 2 * 200 + 2 entries, pop 9 * 40 + 11 + 1 over the first of
 # them (the joint layer's pop does not read por: a plain slice's 11 entries)
-SIZES = dict(pos_of=40, node_at=40, off=41, nbr=400, rk=40, cnt=41, urn=40, **SLICE,
-             deg=40, pop_cnt=41, pop_urn=40, **{"pop_" + k: v for k, v in SLICE.items()})
+SIZES = dict(pos_of=40, node_at=40, off=41, nbr=400, urn=40, **SLICE, rk=40, cnt=41,
+             pop_urn=40, **{"pop_" + k: v for k, v in SLICE.items()}, deg=40, pop_cnt=41)
 SIZES["pop_por"] = 11
 REGIONS = tuple(SIZES)
 
