@@ -234,6 +234,44 @@ int ans_ar_polya_wl_push(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter,
                          const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
 int ans_ar_polya_wl_pop(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, uint32_t *edges,
                         size_t cap, size_t *num_edges);
+/* The same two codecs for graphs with node and edge labels: ShuffleCodec<..SliceCodecs<NodeC, EdgeC, _>,
+ * WLOrbitCodecs<_, N, E, _>> over Graph<N, E, Undirected> (src/recursive/graph/mod.rs:53-104,
+ * slice.rs:33-51, 185-192, src/graph_codec.rs:58-94, incomplete.rs:45-57, 97-151, 193-210).  A label
+ * is a usize under a Categorical: `node` codes node_labels (num_nodes entries by input node), `edge`
+ * codes edge_labels (entry k the label of pair k).  A NULL table is EmptyCodec: that label is absent,
+ * is not coded and feeds no hash; its array must then be NULL too, and a table without its array
+ * is ANS_E_ARG.  With both NULL the bytes are those of ans_ar_er_wl_push / ans_ar_polya_wl_push.
+ * The slice of position v is (its label, the pairs (v, j) with their labels) under the tuple
+ * (NodeC, EdgesIID<EdgeC, indices>), which pushes .1 first: a push of a slice pushes the pairs'
+ * labels in descending order of j (j the position after the step's swap; IID pops them ascending),
+ * then the indices as above, then the node's label; a pop takes the node's label, the indices, sorts
+ * them ascending, then takes a label per index.  In the class of a position, with E(i) the labels of
+ * i's pairs in the prefix graph:
+ *   h_0(i) = hash(label(i), 0) for a known position, hash(0, 1, i) for an unknown one (pop_slice took
+ *            its label out) when nodes carry labels, else as above; with half_iter then
+ *            hash(h_0(i), deg(i), E(i) ascending) when edges carry labels, else as above;
+ *   h_t+1(i) = hash(h_t(i), deg(i), (h_t(j), label(i, j)) for j adjacent to i, the pairs ascending
+ *            lexicographically, two words each) when edges carry labels, else as above.
+ * pop: node_labels receives the label of every position, edges the pairs (v, w) as positions, v
+ * ascending and within v w ascending (the loop first, under either slice model), edge_labels[k] the
+ * label of pair k of edges; the popped graph is the input relabelled by the push's perm.
+ * ANS_E_SYMBOL: a label outside its table; ANS_E_ZERO_MASS: a label of mass 0 (both before a byte
+ * of the message moves); ANS_E_NORM_RANGE: a table whose masses sum to 0.  Else as above. */
+int ans_ar_er_wl_labelled_push(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int wl_iter,
+                               int half_iter, const uint32_t *edges, size_t num_edges,
+                               uint32_t *perm /* NULL, or num_nodes out */, const ans_table *node /* or NULL */,
+                               const ans_table *edge /* or NULL */, const uint32_t *node_labels,
+                               const uint32_t *edge_labels);
+int ans_ar_er_wl_labelled_pop(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int wl_iter,
+                              int half_iter, uint32_t *edges, size_t cap, size_t *num_edges,
+                              const ans_table *node /* or NULL */, const ans_table *edge /* or NULL */,
+                              uint32_t *node_labels /* num_nodes out */, uint32_t *edge_labels /* cap out */);
+int ans_ar_polya_wl_labelled_push(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                                  const uint32_t *edges, size_t num_edges, uint32_t *perm, const ans_table *node,
+                                  const ans_table *edge, const uint32_t *node_labels, const uint32_t *edge_labels);
+int ans_ar_polya_wl_labelled_pop(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                                 uint32_t *edges, size_t cap, size_t *num_edges, const ans_table *node,
+                                 const ans_table *edge, uint32_t *node_labels, uint32_t *edge_labels);
 
 /* ======================================================================
  * (4) GPU bulk path (MI355X / gfx950) — the data-parallel hot path.
@@ -956,6 +994,103 @@ int ans_gpu_ar_polya_wl_pop_graphs(ans_gpu *g, int loops, int wl_iter, int half_
                                    uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens,
                                    uint32_t *out_edges, uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap,
                                    uint64_t *offsets, uint64_t *lens, uint64_t *total);
+
+/* ======================================================================
+ * (5g) The same codecs for graphs with node and edge labels in bulk: ans_ar_er_wl_labelled_push /
+ *      _pop and ans_ar_polya_wl_labelled_push / _pop (section 3) of graph g onto / from the message
+ *      ALREADY in slot g, one lane per graph, under the resume contract exactly as section 5f has it.
+ *      The bytes equal the host codec's.  Tables come from one table set, as ans_gpu_graphs_encode
+ *      has them: bern_table (two symbols: the Erdős–Rényi indicator; the Pólya urn calls take none),
+ *      node_table and edge_table index it, ANS_NO_TABLE = no such label (EmptyCodec).  A label table
+ *      needs its array and an array its table, else ANS_E_ARG.  With both ANS_NO_TABLE the slots,
+ *      lens and perm are those of section 5f; a pop's pairs differ only in that a node's loop comes
+ *      first under the Erdős–Rényi slices too.
+ *        d_node_labels  num_graphs x max_nodes, graph g's labels at g * max_nodes (as d_perm): by input
+ *                       node on a push, by position on a pop;
+ *        d_edge_labels  one entry per pair, at the pairs' offsets: entry d_edge_offsets[g] + k is the
+ *                       label of graph g's pair k.
+ *      Statuses per graph as 5f, and ANS_E_SYMBOL for a label outside its table, ANS_E_ZERO_MASS for
+ *      one of mass 0 (the slot's message is then dropped as for every failing graph: d_lens[g] = 0).
+ *      Slack: ans_gpu_ar_er_wl_labelled_slack / ans_gpu_ar_polya_wl_labelled_slack add to the slack of
+ *      5d / 5e the bytes max_nodes node-label pushes and max_edges edge-label pushes can add: a push
+ *      under a table of norm N and smallest non-zero mass pmin adds fewer than bitlen(N / pmin) bits,
+ *      one more when N > 2^36; a pop takes labels off and adds none.  With
+ *      slot_cap >= d_lens[g] + that slack neither call meets ANS_E_LEN for a slot; the host-buffer
+ *      calls apply it.
+ *      The per-lane state is 5f's with, under an edge table, o grown by max_nodes dwords at wl_iter > 0
+ *      (the sort scratch holds (hash, label) keys of three dwords) and by 2 max_nodes at wl_iter = 0
+ *      (the labels the half iteration sorts), and on a push 2 max_edges + 2 max_nodes dwords more (the
+ *      label of each adjacency entry, the slice's positions and labels).  A node table adds nothing.
+ *      The same 256 MiB rule holds: bounds whose single wave passes it are ANS_E_ARG before anything is
+ *      launched or recorded.  The table set's image is staged in LDS when it is at most 48 KiB.
+ *      Kernel names in ans_gpu_last_launch: k_arer_wll_push(wl_iter=1,half_iter=1,node=1,edge=1),
+ *      k_arer_wll_pop(..), k_arpu_wll_push(..), k_arpu_wll_pop(..).
+ * ====================================================================== */
+int ans_gpu_ar_er_wl_labelled_slack(const ans_gpu_tableset *ts, uint32_t bern_table, uint32_t node_table,
+                                    uint32_t edge_table, uint32_t max_nodes, uint64_t max_edges, int loops,
+                                    uint64_t *bytes);
+int ans_gpu_ar_polya_wl_labelled_slack(const ans_gpu_tableset *ts, uint32_t node_table, uint32_t edge_table,
+                                       uint32_t max_nodes, uint64_t max_edges, uint64_t *bytes);
+int ans_dev_ar_er_wl_labelled_push(ans_gpu_tableset *ts, uint32_t bern_table, uint32_t node_table, uint32_t edge_table,
+                                   int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                   const uint32_t *d_num_nodes, const uint32_t *d_edges, const uint64_t *d_edge_offsets,
+                                   const uint32_t *d_node_labels, const uint32_t *d_edge_labels, uint32_t max_nodes,
+                                   uint64_t max_edges, uint32_t *d_perm /* NULL or num_graphs * max_nodes */,
+                                   uint8_t *d_slots, uint64_t slot_cap, uint32_t *d_lens /* in/out */,
+                                   uint32_t *d_status, void *stream);
+int ans_dev_ar_er_wl_labelled_pop(ans_gpu_tableset *ts, uint32_t bern_table, uint32_t node_table, uint32_t edge_table,
+                                  int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                  const uint32_t *d_num_nodes, uint32_t *d_edges /* out */,
+                                  const uint64_t *d_edge_offsets /* capacities */, uint32_t *d_num_edges /* out */,
+                                  uint32_t *d_node_labels /* out */, uint32_t *d_edge_labels /* out */,
+                                  uint32_t max_nodes, uint64_t max_edges, uint8_t *d_slots /* in/out */,
+                                  uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_ar_polya_wl_labelled_push(ans_gpu_tableset *ts, uint32_t node_table, uint32_t edge_table, int loops,
+                                      int wl_iter, int half_iter, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                                      const uint32_t *d_edges, const uint64_t *d_edge_offsets,
+                                      const uint32_t *d_node_labels, const uint32_t *d_edge_labels, uint32_t max_nodes,
+                                      uint64_t max_edges, uint32_t *d_perm, uint8_t *d_slots, uint64_t slot_cap,
+                                      uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_ar_polya_wl_labelled_pop(ans_gpu_tableset *ts, uint32_t node_table, uint32_t edge_table, int loops,
+                                     int wl_iter, int half_iter, uint64_t num_graphs, const uint32_t *d_num_nodes,
+                                     uint32_t *d_edges /* out */, const uint64_t *d_edge_offsets /* capacities */,
+                                     uint32_t *d_num_edges /* out */, uint32_t *d_node_labels /* out */,
+                                     uint32_t *d_edge_labels /* out */, uint32_t max_nodes, uint64_t max_edges,
+                                     uint8_t *d_slots /* in/out */, uint64_t slot_cap, uint32_t *d_lens /* in/out */,
+                                     uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, exactly as ans_gpu_ar_er_wl_push_graphs / _pop_graphs; node_labels
+ * is num_graphs x the largest num_nodes, graph g's labels at g times that (as perm), edge_labels holds
+ * one entry per pair of edges (a pop: per capacity). */
+int ans_gpu_ar_er_wl_labelled_push_graphs(ans_gpu_tableset *ts, uint32_t bern_table, uint32_t node_table,
+                                          uint32_t edge_table, int loops, int wl_iter, int half_iter,
+                                          uint64_t num_graphs, const uint32_t *num_nodes, const uint32_t *edges,
+                                          const uint64_t *edge_offsets, const uint32_t *node_labels,
+                                          const uint32_t *edge_labels, const uint8_t *in, uint64_t in_len,
+                                          const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *perm,
+                                          uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
+                                          uint64_t *total);
+int ans_gpu_ar_er_wl_labelled_pop_graphs(ans_gpu_tableset *ts, uint32_t bern_table, uint32_t node_table,
+                                         uint32_t edge_table, int loops, int wl_iter, int half_iter,
+                                         uint64_t num_graphs, const uint32_t *num_nodes, const uint64_t *edge_offsets,
+                                         const uint8_t *in, uint64_t in_len, const uint64_t *in_offsets,
+                                         const uint64_t *in_lens, uint32_t *out_edges, uint32_t *out_num_edges,
+                                         uint32_t *out_node_labels, uint32_t *out_edge_labels, uint8_t *out,
+                                         uint64_t out_cap, uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_ar_polya_wl_labelled_push_graphs(ans_gpu_tableset *ts, uint32_t node_table, uint32_t edge_table, int loops,
+                                             int wl_iter, int half_iter, uint64_t num_graphs,
+                                             const uint32_t *num_nodes, const uint32_t *edges,
+                                             const uint64_t *edge_offsets, const uint32_t *node_labels,
+                                             const uint32_t *edge_labels, const uint8_t *in, uint64_t in_len,
+                                             const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *perm,
+                                             uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
+                                             uint64_t *total);
+int ans_gpu_ar_polya_wl_labelled_pop_graphs(ans_gpu_tableset *ts, uint32_t node_table, uint32_t edge_table, int loops,
+                                            int wl_iter, int half_iter, uint64_t num_graphs, const uint32_t *num_nodes,
+                                            const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                                            const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *out_edges,
+                                            uint32_t *out_num_edges, uint32_t *out_node_labels,
+                                            uint32_t *out_edge_labels, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
+                                            uint64_t *lens, uint64_t *total);
 
 #ifdef __cplusplus
 }

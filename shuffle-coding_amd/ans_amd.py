@@ -43,6 +43,7 @@ vp = ctypes.c_void_p
 u64 = ctypes.c_uint64
 sz = ctypes.c_size_t
 ci = ctypes.c_int
+u32 = ctypes.c_uint32
 
 # name -> (restype, argtypes); this list is also the ABI-export test's expectation.
 SIGNATURES = {
@@ -185,6 +186,24 @@ SIGNATURES = {
     "ans_gpu_ar_er_wl_pop_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_ar_polya_wl_push_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_ar_polya_wl_pop_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_ar_er_wl_labelled_push": (ci, [vp, vp, ctypes.c_uint32, ci, ci, ci, vp, sz, vp, vp, vp, vp, vp]),
+    "ans_ar_er_wl_labelled_pop": (ci, [vp, vp, ctypes.c_uint32, ci, ci, ci, vp, sz, ctypes.POINTER(sz), vp, vp, vp, vp]),
+    "ans_ar_polya_wl_labelled_push": (ci, [vp, ctypes.c_uint32, ci, ci, ci, vp, sz, vp, vp, vp, vp, vp]),
+    "ans_ar_polya_wl_labelled_pop": (ci, [vp, ctypes.c_uint32, ci, ci, ci, vp, sz, ctypes.POINTER(sz), vp, vp, vp, vp]),
+    "ans_gpu_ar_er_wl_labelled_slack": (ci, [vp, u32, u32, u32, u32, u64, ci, u64p]),
+    "ans_gpu_ar_polya_wl_labelled_slack": (ci, [vp, u32, u32, u32, u64, u64p]),
+    "ans_dev_ar_er_wl_labelled_push": (ci, [vp, u32, u32, u32, ci, ci, ci, u64, vp, vp, vp, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_er_wl_labelled_pop": (ci, [vp, u32, u32, u32, ci, ci, ci, u64, vp, vp, vp, vp, vp, vp, u32, u64, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_polya_wl_labelled_push": (ci, [vp, u32, u32, ci, ci, ci, u64, vp, vp, vp, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_ar_polya_wl_labelled_pop": (ci, [vp, u32, u32, ci, ci, ci, u64, vp, vp, vp, vp, vp, vp, u32, u64, vp, u64, vp, vp, vp]),
+    "ans_gpu_ar_er_wl_labelled_push_graphs": (ci, [vp, u32, u32, u32, ci, ci, ci, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp,
+                                                   vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_er_wl_labelled_pop_graphs": (ci, [vp, u32, u32, u32, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp,
+                                                  vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_polya_wl_labelled_push_graphs": (ci, [vp, u32, u32, ci, ci, ci, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp,
+                                                      vp, u64, vp, vp, u64p]),
+    "ans_gpu_ar_polya_wl_labelled_pop_graphs": (ci, [vp, u32, u32, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp,
+                                                     vp, u64, vp, vp, u64p]),
     "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
     "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
     "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
@@ -838,6 +857,100 @@ class AutoregressivePolyaWL(AutoregressivePolya):
         _check(lib().ans_ar_polya_wl_pop(m.h, n, self.loops, self.wl_iter, self.half_iter, _np_ptr(out), cap,
                                          ctypes.byref(count)), "AutoregressivePolyaWL::pop")
         return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
+def _graph_arrays(x, node_cat, edge_cat, where):
+    """A Graph symbol as the labelled entries take it: (pairs (E, 2), node labels or None, edge labels
+    or None), each label array present exactly when its codec is."""
+    pairs = _edge_pairs([e for e, _ in x.edges])
+    nl = el = None
+    if node_cat is not None:
+        if any(v is None for v in x.node_labels):
+            raise AnsError(ANS_E_ARG, f"{where}: a node without a label under a node codec")
+        nl = np.ascontiguousarray(np.asarray(list(x.node_labels), dtype=np.uint32).reshape(-1))
+    if edge_cat is not None:
+        if any(l is None for _, l in x.edges):
+            raise AnsError(ANS_E_ARG, f"{where}: an edge without a label under an edge codec")
+        el = np.ascontiguousarray(np.asarray([l for _, l in x.edges], dtype=np.uint32).reshape(-1))
+    return pairs, nl, el
+
+
+def _graph_of(n, pairs, nl, el):
+    """... and back: a Graph of positions from the arrays a labelled pop filled."""
+    return Graph([int(v) for v in nl[:n]] if nl is not None else [None] * n,
+                 [((int(i), int(j)), int(el[k]) if el is not None else None) for k, (i, j) in enumerate(pairs)])
+
+
+class _LabelledOnMessage(Codec):
+    """The host entries of a labelled graph codec (include/ans_capi.h section 3): a symbol is a
+    Graph(node_labels, edges), edges a list of ((i, j), label), i <= j; node / edge_label are
+    Categorical, Uniform or None (EmptyCodec: that label is None in the symbol)."""
+
+    def _labels(self, node, edge_label):
+        self.node_cat, self.edge_cat = _label_categorical(node), _label_categorical(edge_label)
+
+    def _table_args(self):
+        return (self.node_cat.table if self.node_cat is not None else None,
+                self.edge_cat.table if self.edge_cat is not None else None)
+
+    def _push(self, fn, head, m, x, where):
+        pairs, nl, el = _graph_arrays(x, self.node_cat, self.edge_cat, where)
+        if nl is not None and len(nl) != self.num_nodes:
+            raise AnsError(ANS_E_ARG, f"{where}: {self.num_nodes} node labels are needed")
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        nl_, el_ = (a if a is None or a.size else np.zeros(1, np.uint32) for a in (nl, el))
+        _check(fn(m.h, *head, self.num_nodes, self.loops, self.wl_iter, self.half_iter,
+                  _np_ptr(pairs) if len(pairs) else None, len(pairs), _np_ptr(perm), *self._table_args(),
+                  _np_ptr(nl_) if nl_ is not None else None, _np_ptr(el_) if el_ is not None else None), where)
+        return perm[:self.num_nodes]
+
+    def _pop(self, fn, head, m, cap, where):
+        n = self.num_nodes
+        cap = n * (n - 1) // 2 + (n if self.loops else 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        nl = np.zeros(max(n, 1), np.uint32) if self.node_cat is not None else None
+        el = np.zeros(max(cap, 1), np.uint32) if self.edge_cat is not None else None
+        count = sz(0)
+        _check(fn(m.h, *head, n, self.loops, self.wl_iter, self.half_iter, _np_ptr(out), cap, ctypes.byref(count),
+                  *self._table_args(), _np_ptr(nl) if nl is not None else None,
+                  _np_ptr(el) if el is not None else None), where)
+        return _graph_of(n, out[:count.value], nl, el)
+
+
+class AutoregressiveERLabelled(_LabelledOnMessage):
+    """AutoregressiveERWL for graphs with node and edge labels, through ans_ar_er_wl_labelled_push /
+    _pop: ShuffleCodec<ErdosRenyiSliceCodecs<NodeC, EdgeC, _>, WLOrbitCodecs<_, N, E, _>>
+    (src/recursive/graph/slice.rs:16-59, incomplete.rs:45-57, 97-151, 189-236)."""
+
+    def __init__(self, bernoulli, num_nodes, loops, wl_iter=1, half_iter=True, node=None, edge_label=None):
+        self.bernoulli, self.num_nodes, self.loops = bernoulli, num_nodes, bool(loops)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+        self._labels(node, edge_label)
+
+    def push(self, m, x):
+        """Returns perm: perm[position] = the input node the push put there."""
+        return self._push(lib().ans_ar_er_wl_labelled_push, (_two_symbol_table(self.bernoulli).table,), m, x,
+                          "AutoregressiveERLabelled::push")
+
+    def pop(self, m, cap=None):
+        """The Graph of positions: the input relabelled by the push's perm, within a node the pairs ascending."""
+        return self._pop(lib().ans_ar_er_wl_labelled_pop, (_two_symbol_table(self.bernoulli).table,), m, cap,
+                         "AutoregressiveERLabelled::pop")
+
+
+class AutoregressivePolyaLabelled(_LabelledOnMessage):
+    """AutoregressivePolyaWL for graphs with node and edge labels, through ans_ar_polya_wl_labelled_push / _pop."""
+
+    def __init__(self, num_nodes, loops, wl_iter=1, half_iter=True, node=None, edge_label=None):
+        self.num_nodes, self.loops = num_nodes, bool(loops)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+        self._labels(node, edge_label)
+
+    def push(self, m, x):
+        return self._push(lib().ans_ar_polya_wl_labelled_push, (), m, x, "AutoregressivePolyaLabelled::push")
+
+    def pop(self, m, cap=None):
+        return self._pop(lib().ans_ar_polya_wl_labelled_pop, (), m, cap, "AutoregressivePolyaLabelled::pop")
 
 
 # ============================================================== GPU bulk path (section 4)
@@ -1777,6 +1890,134 @@ class GpuAutoregressivePolyaWL(GpuAutoregressivePolya):
                                              _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets),
                                              _dptr(d_num_edges), max_nodes, max_edges, _dptr(d_slots), slot_cap,
                                              _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_ar_polya_wl_pop")
+
+
+class _GpuLabelled:
+    """The bulk calls of a labelled graph codec (include/ans_capi.h 5g): graph g onto / from message g
+    of a container, one lane per graph, under the resume contract.  The tables live in one table set:
+    `first` (the model's own: the Bernoulli), then the node and the edge label's Categorical; `model`
+    is the entries' name part, "er" or "polya"."""
+
+    def _setup(self, gpu, model, first, loops, wl_iter, half_iter, node, edge_label):
+        self.gpu, self.model = gpu, model
+        self.loops, self.wl_iter, self.half_iter = int(bool(loops)), int(wl_iter), int(bool(half_iter))
+        self.node_cat, self.edge_cat = _label_categorical(node), _label_categorical(edge_label)
+        tables = list(first) + [c for c in (self.node_cat, self.edge_cat) if c is not None]
+        # (a set holds at least one table; an unused one-symbol table when the call names none)
+        self.tableset = GpuTableSet(gpu, tables or [Categorical(np.ones(1, np.uint64))])
+        k = len(first)
+        self.t_node = k if self.node_cat is not None else ANS_NO_TABLE
+        self.t_edge = (k + (self.node_cat is not None)) if self.edge_cat is not None else ANS_NO_TABLE
+        self._head = (self.tableset.h,) + tuple(range(k)) + (self.t_node, self.t_edge)
+
+    def _fn(self, what):
+        name = f"ans_{what[0]}_ar_{self.model}_wl_labelled_{what[1]}"
+        return getattr(lib(), name), name
+
+    def slack(self, max_nodes, max_edges):
+        """Bytes a message can grow by during a push or a pop (slot_cap of dev_push / dev_pop)."""
+        b = u64(0)
+        fn, where = self._fn(("gpu", "slack"))
+        tail = (max_nodes, max_edges, self.loops) if self.model == "er" else (max_nodes, max_edges)
+        _check(fn(*self._head, *tail, ctypes.byref(b)), where)
+        return b.value
+
+    def _call(self, what, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        fn, where = self._fn(("gpu", what))
+        _check(fn(*self._head, self.loops, self.wl_iter, self.half_iter, num_graphs, *before, *after, _np_ptr(out), len(out),
+                  _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)), where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def push_graphs(self, graphs, data, offsets, lens):
+        """The push of graphs[g] (a Graph symbol; its node count is len(node_labels)) onto message g of
+        the container (data, offsets, lens), then flatten: returns (list of perms, container of the results)."""
+        where = self._fn(("gpu", "push_graphs"))[1]
+        parts = [_graph_arrays(x, self.node_cat, self.edge_cat, where) for x in graphs]
+        nn, eo = GpuPolyaUrn._shapes(where, [len(x) for x in graphs], [len(p[0]) for p in parts])
+        g = len(nn)
+        width, most = (int(nn.max()), int(np.diff(eo).max())) if g else (0, 0)
+        edges = np.ascontiguousarray(np.concatenate([p[0] for p in parts])) if g and int(eo[-1]) else np.zeros((1, 2), np.uint32)
+        nl = np.zeros((max(g, 1), max(width, 1)), np.uint32) if self.node_cat is not None else None
+        el = np.zeros(max(int(eo[-1]) if g else 0, 1), np.uint32) if self.edge_cat is not None else None
+        for k, (_, n_, e_) in enumerate(parts):
+            if nl is not None:
+                nl[k, :len(n_)] = n_
+            if el is not None:
+                el[int(eo[k]):int(eo[k + 1])] = e_
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        perm = np.zeros((max(g, 1), max(width, 1)), np.uint32)
+        container = self._call(
+            "push_graphs", (_np_ptr(nn), _np_ptr(edges), _np_ptr(eo), _np_ptr(nl) if nl is not None else None,
+                            _np_ptr(el) if el is not None else None),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(perm)), g,
+            data.size + g * self.slack(width, most))
+        return [perm[k, :int(nn[k])] for k in range(g)], container
+
+    def pop_graphs(self, num_nodes, data, offsets, lens, caps=None):
+        """The pop of graph g from message g; caps[g] bounds its pairs (default: every pair of its
+        alphabet).  Returns (list of Graph symbols of positions, container of what remains)."""
+        where = self._fn(("gpu", "pop_graphs"))[1]
+        if caps is None:
+            caps = [int(n) * (int(n) - 1) // 2 + (int(n) if self.loops else 0) for n in num_nodes]
+        nn, eo = GpuPolyaUrn._shapes(where, num_nodes, caps)
+        g = len(nn)
+        width, most = (int(nn.max()), int(np.diff(eo).max())) if g else (0, 0)
+        data, offsets, lens = GpuTableSet._resume_container(where, data, offsets, lens, g)
+        edges = np.zeros((max(int(eo[-1]), 1), 2), np.uint32)
+        counts = np.zeros(max(g, 1), np.uint32)
+        nl = np.zeros((max(g, 1), max(width, 1)), np.uint32) if self.node_cat is not None else None
+        el = np.zeros(max(int(eo[-1]), 1), np.uint32) if self.edge_cat is not None else None
+        container = self._call(
+            "pop_graphs", (_np_ptr(nn), _np_ptr(eo)),
+            (_np_ptr(data) if data.size else None, data.size, _np_ptr(offsets), _np_ptr(lens), _np_ptr(edges),
+             _np_ptr(counts), _np_ptr(nl) if nl is not None else None, _np_ptr(el) if el is not None else None), g,
+            data.size + g * self.slack(width, most))
+        out = []
+        for k in range(g):
+            a, b = int(eo[k]), int(eo[k]) + int(counts[k])
+            out.append(_graph_of(int(nn[k]), edges[a:b], nl[k] if nl is not None else None, el[a:b] if el is not None else None))
+        return out, container
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_node_labels, d_edge_labels, max_nodes,
+                 max_edges, d_slots, slot_cap, d_lens, d_status, stream=None, d_perm=None):
+        """In place on device slots: d_lens is read and rewritten; d_node_labels (num_graphs * max_nodes,
+        by input node) and d_edge_labels (one per pair) are None exactly when their codec is."""
+        fn, where = self._fn(("dev", "push"))
+        _check(fn(*self._head, self.loops, self.wl_iter, self.half_iter, num_graphs, _dptr(d_num_nodes), _dptr(d_edges),
+                  _dptr(d_edge_offsets), _dptr(d_node_labels) if d_node_labels is not None else None,
+                  _dptr(d_edge_labels) if d_edge_labels is not None else None, max_nodes, max_edges,
+                  _dptr(d_perm) if d_perm is not None else None, _dptr(d_slots), slot_cap, _dptr(d_lens),
+                  _dptr(d_status), _sptr(stream)), where)
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, d_node_labels, d_edge_labels,
+                max_nodes, max_edges, d_slots, slot_cap, d_lens, d_status, stream=None):
+        """... d_edges receives graph g's pairs from d_edge_offsets[g] on (the offsets are capacities),
+        d_edge_labels their labels beside them, d_node_labels the labels by position, d_num_edges[g]
+        the pairs' number."""
+        fn, where = self._fn(("dev", "pop"))
+        _check(fn(*self._head, self.loops, self.wl_iter, self.half_iter, num_graphs, _dptr(d_num_nodes), _dptr(d_edges),
+                  _dptr(d_edge_offsets), _dptr(d_num_edges), _dptr(d_node_labels) if d_node_labels is not None else None,
+                  _dptr(d_edge_labels) if d_edge_labels is not None else None, max_nodes, max_edges, _dptr(d_slots),
+                  slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)), where)
+
+
+class GpuAutoregressiveERLabelled(_GpuLabelled):
+    """AutoregressiveERLabelled in bulk (include/ans_capi.h 5g)."""
+
+    def __init__(self, gpu, bernoulli, loops, wl_iter=1, half_iter=True, node=None, edge_label=None):
+        self.bernoulli = bernoulli
+        self._setup(gpu, "er", [_two_symbol_table(bernoulli)], loops, wl_iter, half_iter, node, edge_label)
+
+
+class GpuAutoregressivePolyaLabelled(_GpuLabelled):
+    """AutoregressivePolyaLabelled in bulk (include/ans_capi.h 5g)."""
+
+    def __init__(self, gpu, loops, wl_iter=1, half_iter=True, node=None, edge_label=None):
+        self._setup(gpu, "polya", [], loops, wl_iter, half_iter, node, edge_label)
 
 
 # ============================================================== graph models' bulk caller (section 5)

@@ -7,6 +7,7 @@
 // (ans_pipe.hip for host buffers, ans_kernels.hip for device ones); nothing here is a fallback
 // for it.
 #include <new>
+#include <type_traits>
 
 #include "ans_arer.hpp"
 #include "ans_arpu.hpp"
@@ -497,6 +498,106 @@ int ans_ar_polya_wl_pop(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, 
     const uint64_t room = pop_room(num_nodes, cap);
     return graph_pop<wl::PuPop<VecAcc>>(m, nullptr, WlSetting{wl_iter, half_iter}, wl::pu_pop_entries(num_nodes, room, wl_iter),
                                         num_nodes, room, loops, edges, room, num_edges);
+}
+
+// ---- ... of a graph with node and edge labels (Graph<N, E, Undirected>, N and E each usize or ();
+// src/recursive/graph/mod.rs:53-104, incomplete.rs:45-57, 97-151, 193-210): a NULL table is
+// EmptyCodec, the label absent
+extern "C++" {
+namespace {
+// a table as the recursion's Categorical step takes it; cum keeps the cdf with the norm behind it
+rgraph::Cat host_cat(const ans_table* t, std::vector<uint64_t>& cum) {
+    if (!t) return rgraph::Cat{};
+    check_norm(t->cat.norm());
+    if (t->cat.masses.size() > 0xFFFFFFFFull) throw AnsError(ANS_E_NORM_RANGE, "2^32 or more label symbols");
+    cum = t->cat.cummasses;
+    cum.push_back(t->cat.norm());
+    return rgraph::Cat{cum.data(), nullptr, t->cat.norm(), static_cast<uint32_t>(t->cat.masses.size()), 0};
+}
+template <class F>
+int with_labels(bool node, bool edge, F&& f) {
+    if (node) return edge ? f(rgraph::Labels<true, true>{}) : f(rgraph::Labels<true, false>{});
+    return edge ? f(rgraph::Labels<false, true>{}) : f(rgraph::Labels<false, false, true>{});
+}
+// kEr: the Erdős–Rényi slices under bern, else the Pólya urn's
+template <bool kEr>
+int labelled_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                  const uint32_t* edges, size_t num_edges, uint32_t* perm, const ans_table* node, const ans_table* edge,
+                  const uint32_t* node_labels, const uint32_t* edge_labels) {
+    if (!m || (kEr && !bern) || (num_edges && !edges) || num_edges > rgraph::kMaxEdges || !node != !node_labels ||
+        !edge != !edge_labels)
+        return ANS_E_ARG;
+    return with_labels(node, edge, [&](auto labels) {
+        using L = decltype(labels);
+        using St = std::conditional_t<kEr, wl::ErPush<VecAcc, L>, wl::PuPush<VecAcc, L>>;
+        const uint32_t w = wl_iter >= 0 && wl_iter <= ANS_WL_MAX_ITER ? wl_iter : 0;  // (the setting's check refuses the rest)
+        const uint64_t entries = kEr ? wl::er_push_entries(num_nodes, num_edges, w, L::edge)
+                                     : wl::pu_push_entries(num_nodes, num_edges, w, L::edge);
+        std::vector<uint64_t> node_cum, edge_cum;
+        return graph_host<St>(m, bern, WlSetting{wl_iter, half_iter}, entries, num_nodes, num_edges, [&](auto& c, St& st) {
+            if constexpr (L::any) {
+                st.lab.node = host_cat(node, node_cum);
+                st.lab.edge = host_cat(edge, edge_cum);
+                st.lab.nl = node_labels;
+                st.lab.el = edge_labels;
+            }
+            return rgraph::push_graph(c, st, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
+        });
+    });
+}
+template <bool kEr>
+int labelled_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                 uint32_t* edges, size_t cap, size_t* num_edges, const ans_table* node, const ans_table* edge,
+                 uint32_t* node_labels, uint32_t* edge_labels) {
+    if (!m || (kEr && !bern) || !num_edges || (cap && !edges) || !node != !node_labels || !edge != !edge_labels)
+        return ANS_E_ARG;
+    *num_edges = 0;
+    const uint64_t room = pop_room(num_nodes, cap);
+    return with_labels(node, edge, [&](auto labels) {
+        using L = decltype(labels);
+        using St = std::conditional_t<kEr, wl::ErPop<VecAcc, L>, wl::PuPop<VecAcc, L>>;
+        const uint32_t w = wl_iter >= 0 && wl_iter <= ANS_WL_MAX_ITER ? wl_iter : 0;
+        const uint64_t entries = kEr ? wl::er_pop_entries(num_nodes, room, w, L::edge) : wl::pu_pop_entries(num_nodes, room, w, L::edge);
+        std::vector<uint64_t> node_cum, edge_cum;
+        return graph_host<St>(m, bern, WlSetting{wl_iter, half_iter}, entries, num_nodes, room, [&](auto& c, St& st) {
+            st.lab = rgraph::PopLabels{host_cat(node, node_cum), host_cat(edge, edge_cum), node_labels, edge_labels};
+            uint64_t count = 0;
+            const int rc = rgraph::pop_graph(c, st, num_nodes, loops != 0, edges, room, &count);
+            *num_edges = static_cast<size_t>(count);
+            return rc;
+        });
+    });
+}
+}  // namespace
+}  // extern "C++" (templates)
+
+int ans_ar_er_wl_labelled_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter,
+                               int half_iter, const uint32_t* edges, size_t num_edges, uint32_t* perm,
+                               const ans_table* node, const ans_table* edge, const uint32_t* node_labels,
+                               const uint32_t* edge_labels) {
+    return labelled_push<true>(m, bern, num_nodes, loops, wl_iter, half_iter, edges, num_edges, perm, node, edge,
+                               node_labels, edge_labels);
+}
+
+int ans_ar_er_wl_labelled_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter,
+                              int half_iter, uint32_t* edges, size_t cap, size_t* num_edges, const ans_table* node,
+                              const ans_table* edge, uint32_t* node_labels, uint32_t* edge_labels) {
+    return labelled_pop<true>(m, bern, num_nodes, loops, wl_iter, half_iter, edges, cap, num_edges, node, edge,
+                              node_labels, edge_labels);
+}
+
+int ans_ar_polya_wl_labelled_push(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                                  const uint32_t* edges, size_t num_edges, uint32_t* perm, const ans_table* node,
+                                  const ans_table* edge, const uint32_t* node_labels, const uint32_t* edge_labels) {
+    return labelled_push<false>(m, nullptr, num_nodes, loops, wl_iter, half_iter, edges, num_edges, perm, node, edge,
+                                node_labels, edge_labels);
+}
+
+int ans_ar_polya_wl_labelled_pop(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, uint32_t* edges,
+                                 size_t cap, size_t* num_edges, const ans_table* node, const ans_table* edge,
+                                 uint32_t* node_labels, uint32_t* edge_labels) {
+    return labelled_pop<false>(m, nullptr, num_nodes, loops, wl_iter, half_iter, edges, cap, num_edges, node, edge,
+                               node_labels, edge_labels);
 }
 
 }  // extern "C"

@@ -741,6 +741,7 @@ struct ans_gpu_tableset {
     IndepFast fast;   // ans_mfast.hpp images when every table is in the fast range
     std::vector<uint32_t> nsym;  // symbols per table (host copy: argument checks)
     MsetState* mset = nullptr;   // rank tables of the multiset calls (ans_mset.hip), built on first use
+    std::vector<ans_tab_info> info = {};  // norm, smallest non-zero mass and first mass per table (host copy)
 };
 
 namespace {
@@ -942,6 +943,7 @@ int ans_tableset_build(ans_gpu* g, const Categorical* const* cats, uint32_t ntab
     std::vector<uint64_t> cum;
     std::vector<uint32_t> bkt;
     std::vector<TabHdr> hdr(ntables);
+    std::vector<ans_tab_info> info;
     double max_bits = 0;
     for (uint32_t t = 0; t < ntables; ++t) {
         const Categorical& cat = *cats[t];
@@ -960,6 +962,7 @@ int ans_tableset_build(ans_gpu* g, const Categorical* const* cats, uint32_t ntab
         cum.push_back(norm);
         cum.push_back(norm);  // one past the sentinel: the icdf walk reads c[s + 1] for s <= nsym
         if (pmin != ~0ull) max_bits = std::max(max_bits, std::log2(static_cast<double>(norm) / static_cast<double>(pmin)));
+        info.push_back(ans_tab_info{norm, pmin != ~0ull ? pmin : 0, cat.masses[0]});
         uint32_t bits = 0;
         while (bits < 63 && (1ull << bits) < norm) ++bits;
         h.shift = bits > 12 ? bits - 12 : 0;  // <= 4096 icdf buckets per table
@@ -994,6 +997,7 @@ int ans_tableset_build(ans_gpu* g, const Categorical* const* cats, uint32_t ntab
     }
     ts->nsym.resize(ntables);
     for (uint32_t t = 0; t < ntables; ++t) ts->nsym[t] = hdr[t].nsym;
+    ts->info = std::move(info);
     build_indep_fast(g, cats, ntables, &ts->fast);  // (exact kernels only when it declines)
     *out = ts;
     return ANS_OK;
@@ -1044,6 +1048,7 @@ void ans_tableset_destroy(ans_gpu_tableset* ts) {
 }
 const CatSetModel& ans_tableset_model(const ans_gpu_tableset* ts) { return ts->md; }
 const std::vector<uint32_t>& ans_tableset_nsyms(const ans_gpu_tableset* ts) { return ts->nsym; }
+const std::vector<ans_tab_info>& ans_tableset_info(const ans_gpu_tableset* ts) { return ts->info; }
 MsetState*& ans_tableset_mset(ans_gpu_tableset* ts) { return ts->mset; }
 
 // ---- staging: host buffers in and out

@@ -1,11 +1,11 @@
-// ans_lane.hpp — what the one-lane-per-graph units share.  All four (ans_polya.hip, ans_arer.hip,
-// ans_arpu.hip, ans_wl.hip): the lane-interleaved accessor of a per-graph array in the context's
-// workspace, the message of a push (head + Sink) and of a pop (head + RSource) as polya::Coder takes
-// it, and the launch plan.  The three units of the recursion of ans_rgraph.hpp (ans_arer.hip,
-// ans_arpu.hip, ans_wl.hip) beside: the kernels' arguments, a graph's shape check, the per-lane push
-// and pop loops, the host staging and the argument checks of the entry points, and the context's
-// table of the degrees' class ranks.  Device code and its host launchers; included by those units
-// only.
+// ans_lane.hpp — what the one-lane-per-graph units share.  All five (ans_polya.hip, ans_arer.hip,
+// ans_arpu.hip, ans_wl.hip, ans_wl_labelled.hip): the lane-interleaved accessor of a per-graph array
+// in the context's workspace, the message of a push (head + Sink) and of a pop (head + RSource) as
+// polya::Coder takes it, and the launch plan.  The four units of the recursion of ans_rgraph.hpp
+// (ans_arer.hip, ans_arpu.hip, ans_wl.hip, ans_wl_labelled.hip) beside: the kernels' arguments, a
+// graph's shape check, the per-lane push and pop loops, the host staging and the argument checks of
+// the entry points, and the context's table of the degrees' class ranks.  Device code and its host
+// launchers; included by those units only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -165,13 +165,19 @@ __device__ bool graph_shape(const GraphArgs& a, uint64_t g, uint32_t& n, uint64_
     return true;
 }
 
-// ---- push: grid-stride over the graphs, lane = one graph at a time.  st: an rgraph::PushState.
-template <class St>
-__device__ void push_loop(const GraphArgs& a, const Lane& l, St& st, const uint32_t* edges, uint32_t* perm) {
+// ---- push: grid-stride over the graphs, lane = one graph at a time.  st: an rgraph::PushState;
+// begin(g, e0): what else the state needs of graph g, whose pairs start at e0 (its labels).
+struct NoBegin {
+    __device__ void operator()(uint64_t, uint64_t) const {}
+};
+template <class St, class Begin = NoBegin>
+__device__ void push_loop(const GraphArgs& a, const Lane& l, St& st, const uint32_t* edges, uint32_t* perm,
+                          Begin&& begin = Begin{}) {
     for (uint64_t g = l.id; g < a.num_graphs; g += l.count) {
         uint32_t n = 0;
         uint64_t e0 = 0, E = 0;
         if (!graph_shape<true, false>(a, g, n, e0, E)) continue;
+        begin(g, e0);
         exact::Sink sink(a.slots + g * a.slot_cap, a.slot_cap, a.lens[g]);
         SinkMsg m{0, &sink};  // Message::unflatten: head 0
         polya::Coder<SinkMsg> c{m, ANS_OK};
@@ -192,9 +198,10 @@ __device__ void push_loop(const GraphArgs& a, const Lane& l, St& st, const uint3
 }
 
 // ---- pop: graph g's pairs from edge_offsets[g] of edges on, their number in num_edges[g].  st: an
-// rgraph::PopState.
-template <bool kRoomBounded, class St>
-__device__ void pop_loop(const GraphArgs& a, const Lane& l, St& st, uint32_t* edges, uint32_t* num_edges) {
+// rgraph::PopState; begin as a push's.
+template <bool kRoomBounded, class St, class Begin = NoBegin>
+__device__ void pop_loop(const GraphArgs& a, const Lane& l, St& st, uint32_t* edges, uint32_t* num_edges,
+                         Begin&& begin = Begin{}) {
     for (uint64_t g = l.id; g < a.num_graphs; g += l.count) {
         uint32_t n = 0;
         uint64_t e0 = 0, cap = 0, count = 0;
@@ -202,6 +209,7 @@ __device__ void pop_loop(const GraphArgs& a, const Lane& l, St& st, uint32_t* ed
             num_edges[g] = 0;
             continue;
         }
+        begin(g, e0);
         exact::RSource src{a.slots + g * a.slot_cap, a.slot_cap, a.lens[g], false, false};
         SourceMsg m{0, &src};  // Message::unflatten: head 0
         polya::Coder<SourceMsg> c{m, ANS_OK};

@@ -36,6 +36,10 @@ enum LaunchKind : uint8_t {
     kRecArerWlPop,
     kRecArpuWlPush,
     kRecArpuWlPop,
+    kRecArerWllPush,    // k_arer_wll_push / _pop, k_arpu_wll_push / _pop (ans_wl_labelled.hip)
+    kRecArerWllPop,     //   a = {wl_iter, workgroups, half_iter, node labels, edge labels}
+    kRecArpuWllPush,
+    kRecArpuWllPop,
 };
 struct LaunchRec {
     uint8_t kind;
@@ -45,7 +49,7 @@ struct LaunchRec {
 // The slot of a[] in which a record kind keeps its launch's workgroup count (ans_gpu_last_launch_grid
 // reads it; the text of ans_gpu_last_launch does not show it), or -1 for a kind that keeps none.
 constexpr int rec_grid_slot(uint8_t kind) {
-    return kind >= kRecMsetPush && kind <= kRecArpuWlPop ? 1 : -1;
+    return kind >= kRecMsetPush && kind <= kRecArpuWllPop ? 1 : -1;
 }
 // ... and the count as the slot holds it: the workspace forms launch at most 8 workgroups per CU;
 // the LDS form of the multiset kernels, one lane per chunk, can pass an int16_t and saturates.

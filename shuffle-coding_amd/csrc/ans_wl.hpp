@@ -1,12 +1,13 @@
 // ans_wl.hpp — the orbit stage of recursive shuffle coding on graphs at any wl_iter: the
 // Weisfeiler-Lehman ids of WLOrbitCodecs<GraphPrefix> (src/recursive/graph/incomplete.rs:45-57,
-// 87-151, 189-236) and the PrefixOrbitCodec over them (src/recursive/prefix_orbit.rs), as a stage
-// of the recursion of ans_rgraph.hpp under the autoregressive Erdős–Rényi slices of ans_arer.hpp
-// and the Pólya urn slices of ans_arpu.hpp, one graph on one message.  Plain C++ templated on the
-// message and on how a per-graph array is read and written, host and device alike, so that the host
-// codec (ans_capi.cpp), the kernels (ans_wl.hip) and the CPU tests (g++,
-// tests/native/wl_state_check.cpp) run the same functions. DESIGN.md §3.12 has the restatement with
-// its sources; the comments here say which reference line a step is.
+// 87-151, 189-236) and the PrefixOrbitCodec over them (src/recursive/prefix_orbit.rs), as a stage of
+// the recursion of ans_rgraph.hpp under the autoregressive Erdős–Rényi slices of ans_arer.hpp and the
+// Pólya urn slices of ans_arpu.hpp, one graph on one message.  Plain C++ templated on the message and
+// on how a per-graph array is read and written, host and device alike, so that the host codec
+// (ans_capi.cpp), the kernels (ans_wl.hip, ans_wl_labelled.hip) and the CPU tests (g++,
+// tests/native/wl_state_check.cpp) run the same functions.  DESIGN.md §3.12 has the restatement with
+// its sources, §3.13 the labels (the policy L = rgraph::Labels below); the comments here say which
+// reference line a step is.
 #pragma once
 #include <cstdint>
 
@@ -96,36 +97,104 @@ ANS_MSET_HD void heapsort64(Acc& a, uint32_t n) {
         sift64(a, 0, end);
     }
 }
+// ... and of (hash, label) keys, three entries each, ordered as the tuple (usize, &usize) is.  (Its
+// own loops, not a parameter of the two above: a key of one word keeps the code it had.)
+struct Key {
+    uint64_t h;
+    uint32_t l;
+    ANS_MSET_HD bool operator>(const Key& k) const { return h != k.h ? h > k.h : l > k.l; }
+};
+template <class Acc>
+ANS_MSET_HD Key load_key(const Acc& a, uint32_t i) {
+    return Key{a.load(3 * i) | (uint64_t(a.load(3 * i + 1)) << 32), a.load(3 * i + 2)};
+}
+template <class Acc>
+ANS_MSET_HD void store_key(Acc& a, uint32_t i, const Key& k) {
+    a.store(3 * i, static_cast<uint32_t>(k.h));
+    a.store(3 * i + 1, static_cast<uint32_t>(k.h >> 32));
+    a.store(3 * i + 2, k.l);
+}
+template <class Acc>
+ANS_MSET_HD void sift_keys(Acc& a, uint32_t root, uint32_t n) {
+    const Key v = load_key(a, root);
+    for (;;) {
+        uint32_t child = 2 * root + 1;
+        if (child >= n) break;
+        Key cv = load_key(a, child);
+        if (child + 1 < n) {
+            const Key c2 = load_key(a, child + 1);
+            if (c2 > cv) cv = c2, ++child;
+        }
+        if (!(cv > v)) break;
+        store_key(a, root, cv);
+        root = child;
+    }
+    store_key(a, root, v);
+}
+template <class Acc>
+ANS_MSET_HD void heapsort_keys(Acc& a, uint32_t n) {
+    for (uint32_t s = n / 2; s-- > 0;) sift_keys(a, s, n);
+    for (uint32_t end = n; end-- > 1;) {
+        const Key top = load_key(a, 0);
+        store_key(a, 0, load_key(a, end));
+        store_key(a, end, top);
+        sift_keys(a, 0, end);
+    }
+}
 
 // ---- the prefix graph as the stage reads it
 // On push: the CSR in input labels and the positions; a neighbour counts unless both ends are unknown
 // (pop_slice took those edges out, graph/mod.rs:57-66).
-template <class Acc>
+// With labels (L: rgraph::Labels) each() hands f the pair's label behind the neighbour, and
+// node_label(p) is the label of the node at a known position; without, neither exists.
+using rgraph::Labels;
+using rgraph::NoLabels;
+template <class Acc, class L>
+struct PushAdjLabels {
+    const Acc& elab;     // the label of each entry of nbr
+    const uint32_t* nl;  // the label of an input node
+};
+template <class Acc, bool kSorted>
+struct PushAdjLabels<Acc, Labels<false, false, kSorted>> {};
+template <class Acc, class L = NoLabels>
 struct PushAdj {
     const Acc &pos_of, &node_at, &off, &nbr;
+    PushAdjLabels<Acc, L> lab;
     template <class F>
     ANS_MSET_HD void each(uint32_t p, uint32_t len, F&& f) const {
         const uint32_t u = node_at.load(p);
         for (uint32_t a = off.load(u), end = off.load(u + 1); a < end; ++a) {
             const uint32_t q = pos_of.load(nbr.load(a));
-            if (p < len || q < len) f(q);
+            if (p < len || q < len) {
+                if constexpr (L::edge) f(q, lab.elab.load(a));
+                else f(q);
+            }
         }
     }
     ANS_MSET_HD uint32_t degree(uint32_t p, uint32_t len) const {
         const uint32_t u = node_at.load(p);
         if (p < len) return off.load(u + 1) - off.load(u);
         uint32_t d = 0;
-        each(p, len, [&](uint32_t) { ++d; });
+        each(p, len, [&](uint32_t, auto...) { ++d; });
         return d;
     }
+    ANS_MSET_HD uint32_t node_label(uint32_t p) const { return lab.nl[node_at.load(p)]; }
 };
 // On pop: a list per position over the decoded pairs.  Pair k's ends are the half-edges 2k (out[2k],
 // whose neighbour is out[2k + 1]) and 2k + 1; a loop has the first alone.  Every decoded pair has a
 // known end.
-template <class Acc>
+// The labels are the output arrays': nl[p] of position p, el[k] of pair k.
+template <class L>
+struct PopAdjLabels {
+    const uint32_t *nl, *el;
+};
+template <bool kSorted>
+struct PopAdjLabels<Labels<false, false, kSorted>> {};
+template <class Acc, class L = NoLabels>
 struct PopAdj {
     Acc head, next, deg;  // max_nodes, 2 * max_edges, max_nodes
     const uint32_t* out;
+    PopAdjLabels<L> lab;
     ANS_MSET_HD void clear(uint32_t n) {
         for (uint32_t v = 0; v < n; ++v) {
             head.store(v, kNil);
@@ -144,9 +213,13 @@ struct PopAdj {
     }
     template <class F>
     ANS_MSET_HD void each(uint32_t p, uint32_t, F&& f) const {
-        for (uint32_t e = head.load(p); e != kNil; e = next.load(e)) f(out[e ^ 1u]);
+        for (uint32_t e = head.load(p); e != kNil; e = next.load(e)) {
+            if constexpr (L::edge) f(out[e ^ 1u], lab.el[e >> 1]);
+            else f(out[e ^ 1u]);
+        }
     }
     ANS_MSET_HD uint32_t degree(uint32_t p, uint32_t) const { return deg.load(p); }
+    ANS_MSET_HD uint32_t node_label(uint32_t p) const { return lab.nl[p]; }
 };
 
 // The orbit stage's per-graph state, u32 entries (K = wl_iter + 1 levels):
@@ -157,20 +230,25 @@ struct PopAdj {
 //          cumulative count of the classes below it;  inv[p] = where position p stands in ord
 //   dirty  the positions whose ids a step recomputes, in breadth-first order;  stamp[p] = the step
 //          that listed p
-//   sort   the neighbour hashes of one node, sorted (u64; none at wl_iter = 0)
+//   sort   the neighbour hashes of one node, sorted (u64; none at wl_iter = 0); with edge labels
+//          the (hash, label) keys, three entries each, and at wl_iter = 0 the labels the half
+//          iteration sorts, as u64
 // Insert, remove and change of one position move the entries behind it: O(n) u32 moves each, O(log n)
 // id compares to find the place; the class questions scan the run, O(class size) id compares.
 // An entry's index is a u32: the id store's 2 K max_nodes entries stay below 2^32.
 constexpr bool nodes_ok(uint64_t max_nodes, uint32_t wl_iter) {
     return max_nodes <= 0x7FFFFFFFu && 2 * (uint64_t(wl_iter) + 1) * max_nodes <= 0xFFFFFFFFull;
 }
-constexpr uint64_t orbit_entries(uint64_t max_nodes, uint32_t wl_iter) {
-    return (2 * (uint64_t(wl_iter) + 1) + 4 + (wl_iter ? 2 : 0)) * max_nodes;
+constexpr uint64_t sort_entries(uint64_t max_nodes, uint32_t wl_iter, bool edge_labels) {
+    return (wl_iter ? (edge_labels ? 3 : 2) : (edge_labels ? 2 : 0)) * max_nodes;
+}
+constexpr uint64_t orbit_entries(uint64_t max_nodes, uint32_t wl_iter, bool edge_labels = false) {
+    return (2 * (uint64_t(wl_iter) + 1) + 4) * max_nodes + sort_entries(max_nodes, wl_iter, edge_labels);
 }
 struct Class {
     uint32_t count, cum, index;  // its members, the members of the classes below, its smallest position
 };
-template <class Acc>
+template <class Acc, class L = NoLabels>
 struct Orbits {
     Acc ids, ord, inv, dirty, stamp, sort;
     uint32_t K, half, n, len, m, step, ndirty;  // len known positions, m of them in ord
@@ -182,7 +260,7 @@ struct Orbits {
                  take(max_nodes),
                  take(max_nodes),
                  take(max_nodes),
-                 take(wl_iter ? 2 * max_nodes : 0),
+                 take(sort_entries(max_nodes, wl_iter, L::edge)),
                  wl_iter + 1,
                  half_iter ? 1u : 0u,
                  0,
@@ -211,20 +289,80 @@ struct Orbits {
     // in the prefix graph
     template <class G>
     ANS_MSET_HD void level(const G& g, uint32_t p, uint32_t t) {
+        if constexpr (L::any) {
+            labelled_level(g, p, t);
+        } else {
+            if (t == 0) {
+                // hash((n, if i < len { None } else { Some(i) })): () feeds nothing
+                uint64_t h = p < len ? arer::kH0 : hash2(1, p);
+                if (half) h = hash2(h, g.degree(p, len));  // half_wl_node_iter: h, the Vec<&()>'s length
+                store64(ids, p * K, h);
+                return;
+            }
+            uint32_t deg = 0;
+            g.each(p, len, [&](uint32_t q) { store64(sort, deg++, id(q, t - 1)); });
+            heapsort64(sort, deg);
+            Sip s;  // hash((h, Vec<(usize, &())>)): h, the length, the hashes
+            s.feed(id(p, t - 1));
+            s.feed(deg);
+            for (uint32_t k = 0; k < deg; ++k) s.feed(load64(sort, k));
+            store64(ids, p * K + t, s.finish());
+        }
+    }
+    // ... of a graph with labels: a usize label feeds a word where () feeds nothing.  Level 0 hashes
+    // the node's label (an unknown position's is the default, 0: pop_slice took it out) before the
+    // Option; the half iteration the sorted Vec<&usize> of the pairs' labels behind its length; a
+    // level above the (hash, label) pairs sorted as tuples, two words each.
+    template <class G>
+    ANS_MSET_HD void labelled_level(const G& g, uint32_t p, uint32_t t) {
         if (t == 0) {
-            // hash((n, if i < len { None } else { Some(i) })): () feeds nothing
-            uint64_t h = p < len ? arer::kH0 : hash2(1, p);
-            if (half) h = hash2(h, g.degree(p, len));  // half_wl_node_iter: h, the Vec<&()>'s length
+            uint64_t h = 0;
+            if constexpr (L::node) {
+                Sip s;
+                s.feed(p < len ? g.node_label(p) : 0);
+                s.feed(p < len ? 0 : 1);
+                if (p >= len) s.feed(p);
+                h = s.finish();
+            } else {
+                h = p < len ? arer::kH0 : hash2(1, p);
+            }
+            if (half) {
+                if constexpr (L::edge) {
+                    uint32_t deg = 0;
+                    g.each(p, len, [&](uint32_t, uint32_t label) { store64(sort, deg++, label); });
+                    heapsort64(sort, deg);
+                    Sip s;
+                    s.feed(h);
+                    s.feed(deg);
+                    for (uint32_t k = 0; k < deg; ++k) s.feed(load64(sort, k));
+                    h = s.finish();
+                } else {
+                    h = hash2(h, g.degree(p, len));
+                }
+            }
             store64(ids, p * K, h);
             return;
         }
         uint32_t deg = 0;
-        g.each(p, len, [&](uint32_t q) { store64(sort, deg++, id(q, t - 1)); });
-        heapsort64(sort, deg);
-        Sip s;  // hash((h, Vec<(usize, &())>)): h, the length, the hashes
+        Sip s;
+        if constexpr (L::edge) {
+            g.each(p, len, [&](uint32_t q, uint32_t label) { store_key(sort, deg++, Key{id(q, t - 1), label}); });
+            heapsort_keys(sort, deg);
+        } else {
+            g.each(p, len, [&](uint32_t q) { store64(sort, deg++, id(q, t - 1)); });
+            heapsort64(sort, deg);
+        }
         s.feed(id(p, t - 1));
         s.feed(deg);
-        for (uint32_t k = 0; k < deg; ++k) s.feed(load64(sort, k));
+        for (uint32_t k = 0; k < deg; ++k) {
+            if constexpr (L::edge) {
+                const Key key = load_key(sort, k);
+                s.feed(key.h);
+                s.feed(key.l);
+            } else {
+                s.feed(load64(sort, k));
+            }
+        }
         store64(ids, p * K + t, s.finish());
     }
 
@@ -297,7 +435,7 @@ struct Orbits {
             // the positions at distance t (:103-111), then level t of everything within it (:127-145:
             // level t reads level t - 1 alone, which is final by now, so the ids are written in place)
             const uint32_t to = ndirty;
-            for (uint32_t k = from; k < to; ++k) g.each(dirty.load(k), len, [&](uint32_t q) { touch(q); });
+            for (uint32_t k = from; k < to; ++k) g.each(dirty.load(k), len, [&](uint32_t q, auto...) { touch(q); });
             from = to;
             for (uint32_t k = 0; k < ndirty; ++k) level(g, dirty.load(k), t);
         }
@@ -323,8 +461,9 @@ struct Orbits {
     }
     // ---- what the recursion of ans_rgraph.hpp asks of an orbit stage on a push (g: its PushGraph)
     template <class G>
-    ANS_MSET_HD static PushAdj<Acc> adj_of(const G& g) {
-        return PushAdj<Acc>{g.pos_of, g.node_at, g.off, g.nbr};
+    ANS_MSET_HD static PushAdj<Acc, L> adj_of(const G& g) {
+        if constexpr (L::any) return PushAdj<Acc, L>{g.pos_of, g.node_at, g.off, g.nbr, {g.lab.elab, g.lab.nl}};
+        else return PushAdj<Acc, L>{g.pos_of, g.node_at, g.off, g.nbr, {}};
     }
     ANS_MSET_HD bool coded() const { return true; }
     template <class G>
@@ -332,11 +471,11 @@ struct Orbits {
         apply(adj_of(g), nodes, nodes);
         begin();
     }
-    // the blanket pop under norm L and the class's smallest position (recursive/mod.rs:123-127)
+    // the blanket pop under norm `known` and the class's smallest position (recursive/mod.rs:123-127)
     template <class M>
-    ANS_MSET_HD int pop_element(polya::Coder<M>& c, uint32_t L, uint32_t& index, uint32_t&) {
+    ANS_MSET_HD int pop_element(polya::Coder<M>& c, uint32_t known, uint32_t& index, uint32_t&) {
         uint64_t q = 0, cf = 0;
-        if (!c.pop_begin(L, q, cf)) return c.err;
+        if (!c.pop_begin(known, q, cf)) return c.err;
         const Class f = find(cf);
         c.pop_end(f.count, q, cf - f.cum);
         index = f.index;
@@ -354,15 +493,19 @@ struct Orbits {
 
 // The stage of a pop: the decoded prefix's adjacency and the ids over it.  cap is at most the
 // max_edges of the state.
-template <class Acc>
+template <class Acc, class L = NoLabels>
 struct PopOrbits {
-    PopAdj<Acc> adj;
-    Orbits<Acc> orb;
+    PopAdj<Acc, L> adj;
+    Orbits<Acc, L> orb;
     template <class Take>
     ANS_MSET_HD static PopOrbits make(Take& take, uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter, bool half_iter) {
-        PopOrbits o{{take(max_nodes), take(2 * max_edges), take(max_nodes), nullptr},
-                    Orbits<Acc>::make(take, max_nodes, max_edges, wl_iter, half_iter)};
+        PopOrbits o{{take(max_nodes), take(2 * max_edges), take(max_nodes), nullptr, {}},
+                    Orbits<Acc, L>::make(take, max_nodes, max_edges, wl_iter, half_iter)};
         return o;
+    }
+    ANS_MSET_HD void start_pop(uint32_t n, const uint32_t* out, const uint32_t* nl, const uint32_t* el) {
+        adj.lab = PopAdjLabels<L>{nl, el};
+        start_pop(n, out);
     }
     ANS_MSET_HD void start_pop(uint32_t n, const uint32_t* out) {
         adj.out = out;
@@ -392,26 +535,32 @@ using rgraph::build_csr;
 
 // ---- the per-graph states (ans_rgraph.hpp lays them out: on a push the prefix graph, the slice
 // model's arrays, the ids; on a pop the slice model's arrays, the decoded adjacency, the ids)
-constexpr uint64_t er_push_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter) {
-    return rgraph::graph_entries(max_nodes, max_edges) + max_nodes + orbit_entries(max_nodes, wl_iter);
+// Edge labels add to a push the label of each CSR entry and the slice's two arrays
+// (rgraph::push_label_entries: 2 max_edges + 2 max_nodes), and to both a wider sort scratch
+// (sort_entries: max_nodes more at wl_iter >= 1, 2 max_nodes at wl_iter = 0); node labels add nothing.
+constexpr uint64_t er_push_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter, bool edge_labels = false) {
+    return rgraph::graph_entries(max_nodes, max_edges) + max_nodes + orbit_entries(max_nodes, wl_iter, edge_labels) +
+           rgraph::push_label_entries(max_nodes, max_edges, edge_labels);
 }
-constexpr uint64_t er_pop_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter) {
-    return pop_adj_entries(max_nodes, max_edges) + orbit_entries(max_nodes, wl_iter);
+constexpr uint64_t er_pop_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter, bool edge_labels = false) {
+    return pop_adj_entries(max_nodes, max_edges) + orbit_entries(max_nodes, wl_iter, edge_labels);
 }
-constexpr uint64_t pu_push_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter) {
-    return rgraph::graph_entries(max_nodes, max_edges) + arpu::model_entries(max_nodes, true) + orbit_entries(max_nodes, wl_iter);
+constexpr uint64_t pu_push_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter, bool edge_labels = false) {
+    return rgraph::graph_entries(max_nodes, max_edges) + arpu::model_entries(max_nodes, true) +
+           orbit_entries(max_nodes, wl_iter, edge_labels) + rgraph::push_label_entries(max_nodes, max_edges, edge_labels);
 }
-constexpr uint64_t pu_pop_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter) {
-    return arpu::model_entries(max_nodes, false) + pop_adj_entries(max_nodes, max_edges) + orbit_entries(max_nodes, wl_iter);
+constexpr uint64_t pu_pop_entries(uint64_t max_nodes, uint64_t max_edges, uint32_t wl_iter, bool edge_labels = false) {
+    return arpu::model_entries(max_nodes, false) + pop_adj_entries(max_nodes, max_edges) +
+           orbit_entries(max_nodes, wl_iter, edge_labels);
 }
-template <class Acc>
-using ErPush = rgraph::PushState<Acc, arer::ErSlices<Acc>, Orbits<Acc>>;
-template <class Acc>
-using ErPop = rgraph::PopState<Acc, arer::ErSlices<Acc>, PopOrbits<Acc>>;
-template <class Acc>
-using PuPush = rgraph::PushState<Acc, arpu::PuSlices<Acc>, Orbits<Acc>>;
-template <class Acc>
-using PuPop = rgraph::PopState<Acc, arpu::PuSlices<Acc>, PopOrbits<Acc>>;
+template <class Acc, class L = NoLabels>
+using ErPush = rgraph::PushState<Acc, arer::ErSlices<Acc>, Orbits<Acc, L>, L>;
+template <class Acc, class L = NoLabels>
+using ErPop = rgraph::PopState<Acc, arer::ErSlices<Acc>, PopOrbits<Acc, L>, L>;
+template <class Acc, class L = NoLabels>
+using PuPush = rgraph::PushState<Acc, arpu::PuSlices<Acc>, Orbits<Acc, L>, L>;
+template <class Acc, class L = NoLabels>
+using PuPop = rgraph::PopState<Acc, arpu::PuSlices<Acc>, PopOrbits<Acc, L>, L>;
 
 }  // namespace wl
 }  // namespace shuffle_coding
