@@ -234,6 +234,33 @@ int ans_ar_polya_wl_push(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter,
                          const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
 int ans_ar_polya_wl_pop(ans_msg *m, uint32_t num_nodes, int loops, int wl_iter, int half_iter, uint32_t *edges,
                         size_t cap, size_t *num_edges);
+/* Joint shuffle coding of the same graph: ShuffleCodec<JointSliceCodecs<C>, WLOrbitCodecs<JointPrefix<_>>>
+ * (src/recursive/joint.rs, src/recursive/mod.rs:117-148, src/recursive/graph/incomplete.rs:154-187,
+ * src/graph_codec.rs:405-450).  The graph is coded whole by an ordered codec C and the order of its
+ * nodes is taken back through the orbit codecs above.  push: the ids of the full graph; num_nodes times
+ * the blanket pop of a class under norm len, its smallest position swapped with position len - 1, which
+ * leaves the known ones, and the ids updated around it; then C pushes the permuted graph.  pop: C's
+ * graph, the ids with every position unknown, then num_nodes times a position joins, the ids are
+ * updated around it and its class is pushed.  The classes are those of ans_ar_er_wl_push with two
+ * differences: the prefix graph keeps every edge (a neighbour counts even when both ends are unknown,
+ * deg(i) is the full degree), and only the position that changed sides is at distance 0 of an update.
+ * perm and the statuses are those of ans_ar_er_wl_push / _pop.  A failed call leaves the message as
+ * it found it.
+ *   ans_joint_er_wl_*:    C = GraphIID<EmptyCodec, EmptyCodec, ErdosRenyi<Undirected>>, IID<Bernoulli> over
+ *     AllEdgeIndices (src/graph_codec.rs:104-139, 184-199): the loops (i, i) by i when `loops`, then
+ *     the pairs (i, j), i < j, by j, then by i; the last slot is pushed first.  pop: edges receives
+ *     the pairs in that order, *num_edges their number; more than cap of them is ANS_E_LEN.
+ *   ans_joint_polya_wl_*: C = polya_urn(num_nodes, num_edges, loops, redraws), ans_polya_push / _pop
+ *     unchanged on the pairs of positions.  num_edges is a parameter of the codec: a pop takes it and
+ *     edges receives that many pairs as ans_polya_pop gives them. */
+int ans_joint_er_wl_push(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                         const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
+int ans_joint_er_wl_pop(ans_msg *m, const ans_table *bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                        uint32_t *edges, size_t cap, size_t *num_edges);
+int ans_joint_polya_wl_push(ans_msg *m, uint32_t num_nodes, int loops, int redraws, int wl_iter, int half_iter,
+                            const uint32_t *edges, size_t num_edges, uint32_t *perm /* NULL, or num_nodes out */);
+int ans_joint_polya_wl_pop(ans_msg *m, uint32_t num_nodes, int loops, int redraws, int wl_iter, int half_iter,
+                           uint32_t *edges, size_t num_edges);
 /* The same two codecs for graphs with node and edge labels: ShuffleCodec<..SliceCodecs<NodeC, EdgeC, _>,
  * WLOrbitCodecs<_, N, E, _>> over Graph<N, E, Undirected> (src/recursive/graph/mod.rs:53-104,
  * slice.rs:33-51, 185-192, src/graph_codec.rs:58-94, incomplete.rs:45-57, 97-151, 193-210).  A label
@@ -1091,6 +1118,78 @@ int ans_gpu_ar_polya_wl_labelled_pop_graphs(ans_gpu_tableset *ts, uint32_t node_
                                             uint32_t *out_num_edges, uint32_t *out_node_labels,
                                             uint32_t *out_edge_labels, uint8_t *out, uint64_t out_cap, uint64_t *offsets,
                                             uint64_t *lens, uint64_t *total);
+
+/* ======================================================================
+ * (5h) Joint shuffle coding of graphs in bulk: ans_joint_er_wl_push / _pop and ans_joint_polya_wl_push /
+ *      _pop (section 3) of graph g onto / from the message ALREADY in slot g, one lane per graph, under
+ *      the resume contract exactly as section 5f has it (slots, d_lens, d_perm, d_num_edges, the
+ *      statuses OR-ed into *d_status with d_lens[g] = 0 for the failing graph alone).  The bytes equal
+ *      the host codec's.  wl_iter above ANS_WL_MAX_ITER is ANS_E_ARG.  On an Erdős–Rényi pop the
+ *      offsets are CAPACITIES and a graph's state holds min(capacity, max_edges) pairs; one more is
+ *      ANS_E_LEN for that graph.  On a Pólya urn pop the offsets give each graph's pair count (the
+ *      codec's parameter; more than max_edges is ANS_E_ARG for that graph) and d_num_edges[g]
+ *      receives it back, 0 for a failing graph.
+ *      Slack: a push's orbit pops add nothing and its ordered push what the ordered codec's bound says;
+ *      a pop's orbit pushes add at most bitlen(max_nodes) bits each.  ans_gpu_joint_er_slack equals
+ *      ans_gpu_ar_er_slack (the same indicators on a push, the same orbit pushes on a pop);
+ *      ans_gpu_joint_polya_slack is ans_gpu_polya_slack plus max_nodes * bitlen(max_nodes) / 8 + 1 +
+ *      (max_nodes >> 20) bytes.  With slot_cap >= d_lens[g] + that slack
+ *      neither call meets ANS_E_LEN for a slot.  The host-buffer calls apply it.
+ *      The per-lane state, with K = wl_iter + 1: the orbit stage is 5f's but for its dirty list, which
+ *      holds one position at wl_iter = 0 (an update starts from one position): o = (2K + 6) max_nodes
+ *      dwords at wl_iter > 0 and 5 max_nodes + 1 at wl_iter = 0 (0 without nodes).  The ordered codec
+ *      and the orbit stage never run at the same time, so the urn's arrays (section 5c) lie over the orbit
+ *      stage's: u = 2 max_nodes + 6 max_edges + 2 dwords on a push and 2 max_nodes + 5 max_edges + 2 +
+ *      min(max_edges, 11) on a pop.  Erdős–Rényi push 3 max_nodes + 2 max_edges + 1 + o, pop
+ *      2 max_nodes + 2 max_edges + o; Pólya urn push 3 max_nodes + 2 max_edges + 1 + max(o, u), pop
+ *      max(2 max_nodes + 2 max_edges + o, u).  The same 256 MiB rule holds.
+ *      Kernel names in ans_gpu_last_launch: k_joint_er_push(wl_iter=1,half_iter=1), k_joint_er_pop(..),
+ *      k_joint_pu_push(wl_iter=1,half_iter=1,redraws=0), k_joint_pu_pop(..).
+ * ====================================================================== */
+int ans_gpu_joint_er_slack(const ans_gpu_table *gt, uint32_t max_nodes, int loops, uint64_t *bytes);
+int ans_gpu_joint_polya_slack(uint32_t max_nodes, uint64_t max_edges, uint64_t *bytes);
+int ans_dev_joint_er_wl_push(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                             const uint32_t *d_num_nodes, const uint32_t *d_edges, const uint64_t *d_edge_offsets,
+                             uint32_t max_nodes, uint64_t max_edges, uint32_t *d_perm /* NULL or num_graphs * max_nodes */,
+                             uint8_t *d_slots, uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status,
+                             void *stream);
+int ans_dev_joint_er_wl_pop(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                            const uint32_t *d_num_nodes, uint32_t *d_edges /* out */,
+                            const uint64_t *d_edge_offsets /* capacities */, uint32_t *d_num_edges /* out */,
+                            uint32_t max_nodes, uint64_t max_edges, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                            uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_joint_polya_wl_push(ans_gpu *g, int loops, int redraws, int wl_iter, int half_iter, uint64_t num_graphs,
+                                const uint32_t *d_num_nodes, const uint32_t *d_edges, const uint64_t *d_edge_offsets,
+                                uint32_t max_nodes, uint64_t max_edges, uint32_t *d_perm, uint8_t *d_slots,
+                                uint64_t slot_cap, uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+int ans_dev_joint_polya_wl_pop(ans_gpu *g, int loops, int redraws, int wl_iter, int half_iter, uint64_t num_graphs,
+                               const uint32_t *d_num_nodes, uint32_t *d_edges /* out */,
+                               const uint64_t *d_edge_offsets /* the pair counts */, uint32_t *d_num_edges /* out */,
+                               uint32_t max_nodes, uint64_t max_edges, uint8_t *d_slots /* in/out */, uint64_t slot_cap,
+                               uint32_t *d_lens /* in/out */, uint32_t *d_status, void *stream);
+/* ... on host buffers, synchronous, exactly as ans_gpu_ar_er_wl_push_graphs / _pop_graphs. */
+int ans_gpu_joint_er_wl_push_graphs(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                    const uint32_t *num_nodes, const uint32_t *edges, const uint64_t *edge_offsets,
+                                    const uint8_t *in, uint64_t in_len, const uint64_t *in_offsets,
+                                    const uint64_t *in_lens, uint32_t *perm, uint8_t *out, uint64_t out_cap,
+                                    uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_joint_er_wl_pop_graphs(ans_gpu_table *gt, int loops, int wl_iter, int half_iter, uint64_t num_graphs,
+                                   const uint32_t *num_nodes, const uint64_t *edge_offsets, const uint8_t *in,
+                                   uint64_t in_len, const uint64_t *in_offsets, const uint64_t *in_lens,
+                                   uint32_t *out_edges, uint32_t *out_num_edges, uint8_t *out, uint64_t out_cap,
+                                   uint64_t *offsets, uint64_t *lens, uint64_t *total);
+int ans_gpu_joint_polya_wl_push_graphs(ans_gpu *g, int loops, int redraws, int wl_iter, int half_iter,
+                                       uint64_t num_graphs, const uint32_t *num_nodes, const uint32_t *edges,
+                                       const uint64_t *edge_offsets, const uint8_t *in, uint64_t in_len,
+                                       const uint64_t *in_offsets, const uint64_t *in_lens, uint32_t *perm,
+                                       uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
+                                       uint64_t *total);
+int ans_gpu_joint_polya_wl_pop_graphs(ans_gpu *g, int loops, int redraws, int wl_iter, int half_iter,
+                                      uint64_t num_graphs, const uint32_t *num_nodes, const uint64_t *edge_offsets,
+                                      const uint8_t *in, uint64_t in_len, const uint64_t *in_offsets,
+                                      const uint64_t *in_lens, uint32_t *out_edges, uint32_t *out_num_edges,
+                                      uint8_t *out, uint64_t out_cap, uint64_t *offsets, uint64_t *lens,
+                                      uint64_t *total);
 
 #ifdef __cplusplus
 }

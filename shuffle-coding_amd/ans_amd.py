@@ -204,6 +204,20 @@ SIGNATURES = {
                                                       vp, u64, vp, vp, u64p]),
     "ans_gpu_ar_polya_wl_labelled_pop_graphs": (ci, [vp, u32, u32, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp,
                                                      vp, u64, vp, vp, u64p]),
+    "ans_joint_er_wl_push": (ci, [vp, vp, ctypes.c_uint32, ci, ci, ci, vp, sz, vp]),
+    "ans_joint_er_wl_pop": (ci, [vp, vp, ctypes.c_uint32, ci, ci, ci, vp, sz, ctypes.POINTER(sz)]),
+    "ans_joint_polya_wl_push": (ci, [vp, ctypes.c_uint32, ci, ci, ci, ci, vp, sz, vp]),
+    "ans_joint_polya_wl_pop": (ci, [vp, ctypes.c_uint32, ci, ci, ci, ci, vp, sz]),
+    "ans_gpu_joint_er_slack": (ci, [vp, u32, ci, u64p]),
+    "ans_gpu_joint_polya_slack": (ci, [u32, u64, u64p]),
+    "ans_dev_joint_er_wl_push": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_joint_er_wl_pop": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_dev_joint_polya_wl_push": (ci, [vp, ci, ci, ci, ci, u64, vp, vp, vp, ctypes.c_uint32, u64, vp, vp, u64, vp, vp, vp]),
+    "ans_dev_joint_polya_wl_pop": (ci, [vp, ci, ci, ci, ci, u64, vp, vp, vp, vp, ctypes.c_uint32, u64, vp, u64, vp, vp, vp]),
+    "ans_gpu_joint_er_wl_push_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_joint_er_wl_pop_graphs": (ci, [vp, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_joint_polya_wl_push_graphs": (ci, [vp, ci, ci, ci, ci, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, u64p]),
+    "ans_gpu_joint_polya_wl_pop_graphs": (ci, [vp, ci, ci, ci, ci, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64p]),
     "ans_gpu_mset_pop_slack": (ci, [u64, u64p]),
     "ans_dev_mset_push": (ci, [vp, ctypes.c_uint32, vp, ci, u64, u64, vp, u64, vp, vp, vp]),
     "ans_dev_mset_pop": (ci, [vp, ctypes.c_uint32, vp, u64, vp, u64, u64, vp, ci, vp, vp]),
@@ -857,6 +871,59 @@ class AutoregressivePolyaWL(AutoregressivePolya):
         _check(lib().ans_ar_polya_wl_pop(m.h, n, self.loops, self.wl_iter, self.half_iter, _np_ptr(out), cap,
                                          ctypes.byref(count)), "AutoregressivePolyaWL::pop")
         return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
+class JointERWL(Codec):
+    """Joint shuffle coding of an undirected, unlabelled graph: ShuffleCodec<JointSliceCodecs<C>,
+    WLOrbitCodecs<JointPrefix<_>>> (src/recursive/joint.rs, src/recursive/graph/incomplete.rs:154-187) with
+    C = GraphIID<EmptyCodec, EmptyCodec, ErdosRenyi> (the dense indicator over AllEdgeIndices), through
+    ans_joint_er_wl_push / _pop.  A symbol is the graph's edges as pairs (i, j), i <= j."""
+
+    def __init__(self, bernoulli, num_nodes, loops, wl_iter=1, half_iter=True):
+        self.bernoulli, self.num_nodes, self.loops = bernoulli, num_nodes, bool(loops)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+
+    def push(self, m, x):
+        """Returns perm: perm[position] = the input node the push put there."""
+        e = _edge_pairs(list(x))
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        _check(lib().ans_joint_er_wl_push(m.h, _two_symbol_table(self.bernoulli).table, self.num_nodes, self.loops,
+                                          self.wl_iter, self.half_iter, _np_ptr(e) if len(e) else None, len(e),
+                                          _np_ptr(perm)), "JointERWL::push")
+        return perm[:self.num_nodes]
+
+    def pop(self, m, cap=None):
+        """The pairs of positions in the order of AllEdgeIndices; the input relabelled by the push's perm."""
+        n = self.num_nodes
+        cap = n * (n - 1) // 2 + (n if self.loops else 0) if cap is None else cap
+        out = np.zeros((max(cap, 1), 2), np.uint32)
+        count = sz(0)
+        _check(lib().ans_joint_er_wl_pop(m.h, _two_symbol_table(self.bernoulli).table, n, self.loops, self.wl_iter,
+                                         self.half_iter, _np_ptr(out), cap, ctypes.byref(count)), "JointERWL::pop")
+        return [(int(i), int(j)) for i, j in out[:count.value]]
+
+
+class JointPolyaWL(Codec):
+    """JointERWL with C = polya_urn(num_nodes, num_edges, loops, redraws) (PolyaUrn), through
+    ans_joint_polya_wl_push / _pop.  The edge count is a parameter of the codec: pop takes it."""
+
+    def __init__(self, num_nodes, loops, redraws, wl_iter=1, half_iter=True):
+        self.num_nodes, self.loops, self.redraws = num_nodes, bool(loops), bool(redraws)
+        self.wl_iter, self.half_iter = int(wl_iter), int(bool(half_iter))
+
+    def push(self, m, x):
+        e = _edge_pairs(list(x))
+        perm = np.zeros(max(self.num_nodes, 1), np.uint32)
+        _check(lib().ans_joint_polya_wl_push(m.h, self.num_nodes, self.loops, self.redraws, self.wl_iter, self.half_iter,
+                                             _np_ptr(e) if len(e) else None, len(e), _np_ptr(perm)), "JointPolyaWL::push")
+        return perm[:self.num_nodes]
+
+    def pop(self, m, num_edges):
+        """The num_edges pairs of positions as PolyaUrn::pop gives them (sorted up to 11, in pop order beyond)."""
+        out = np.zeros((max(num_edges, 1), 2), np.uint32)
+        _check(lib().ans_joint_polya_wl_pop(m.h, self.num_nodes, self.loops, self.redraws, self.wl_iter, self.half_iter,
+                                            _np_ptr(out), num_edges), "JointPolyaWL::pop")
+        return [(int(i), int(j)) for i, j in out[:num_edges]]
 
 
 def _graph_arrays(x, node_cat, edge_cat, where):
@@ -1890,6 +1957,81 @@ class GpuAutoregressivePolyaWL(GpuAutoregressivePolya):
                                              _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets),
                                              _dptr(d_num_edges), max_nodes, max_edges, _dptr(d_slots), slot_cap,
                                              _dptr(d_lens), _dptr(d_status), _sptr(stream)), "ans_dev_ar_polya_wl_pop")
+
+
+class GpuJointERWL(GpuAutoregressiveERWL):
+    """JointERWL in bulk (include/ans_capi.h 5h): GpuAutoregressiveERWL's calls on the joint codec; a pop
+    gives a graph's pairs in the order of AllEdgeIndices."""
+
+    def slack(self, max_nodes):
+        b = u64(0)
+        _check(lib().ans_gpu_joint_er_slack(self.table.h, max_nodes, self.loops, ctypes.byref(b)), "ans_gpu_joint_er_slack")
+        return b.value
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        return super()._call(where.replace("ans_gpu_ar_er_", "ans_gpu_joint_er_wl_"), fn, before, after, num_graphs, cap)
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None, d_perm=None):
+        _check(lib().ans_dev_joint_er_wl_push(self.table.h, self.loops, self.wl_iter, self.half_iter, num_graphs,
+                                              _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets), max_nodes,
+                                              max_edges, _dptr(d_perm) if d_perm is not None else None, _dptr(d_slots),
+                                              slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_joint_er_wl_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, max_nodes, max_edges, d_slots,
+                slot_cap, d_lens, d_status, stream=None):
+        _check(lib().ans_dev_joint_er_wl_pop(self.table.h, self.loops, self.wl_iter, self.half_iter, num_graphs,
+                                             _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets), _dptr(d_num_edges),
+                                             max_nodes, max_edges, _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status),
+                                             _sptr(stream)), "ans_dev_joint_er_wl_pop")
+
+
+class GpuJointPolyaWL(GpuAutoregressivePolya):
+    """JointPolyaWL in bulk (include/ans_capi.h 5h).  A pop takes each graph's edge count: the offsets of
+    dev_pop are the counts' running sums, and d_num_edges gives the counts back (0 for a failing graph)."""
+
+    def __init__(self, gpu, loops, redraws, wl_iter=1, half_iter=True):
+        super().__init__(gpu, loops, ORBITS_DEGREE if half_iter else ORBITS_ONE_CLASS)
+        self.redraws, self.wl_iter, self.half_iter = int(bool(redraws)), int(wl_iter), int(bool(half_iter))
+
+    @staticmethod
+    def slack(max_nodes, max_edges):
+        b = u64(0)
+        _check(lib().ans_gpu_joint_polya_slack(max_nodes, max_edges, ctypes.byref(b)), "ans_gpu_joint_polya_slack")
+        return b.value
+
+    def _call(self, where, fn, before, after, num_graphs, cap):
+        out = np.empty(max(cap, 1), np.uint8)
+        offsets = np.zeros(max(num_graphs, 1), np.uint64)
+        lens = np.zeros(max(num_graphs, 1), np.uint64)
+        total = u64(0)
+        where = where.replace("ans_gpu_ar_polya_", "ans_gpu_joint_polya_wl_")
+        _check(getattr(lib(), where)(self.gpu.h, self.loops, self.redraws, self.wl_iter, self.half_iter, num_graphs, *before,
+                                     *after, _np_ptr(out), len(out), _np_ptr(offsets), _np_ptr(lens), ctypes.byref(total)),
+               where)
+        return out[:total.value], offsets[:num_graphs], lens[:num_graphs]
+
+    def pop_graphs(self, num_nodes, num_edges, data, offsets, lens):
+        """JointPolyaWL::pop of num_edges[g] pairs from message g: returns (list of (E_g, 2) arrays of
+        positions, container of what remains)."""
+        return super().pop_graphs(num_nodes, data, offsets, lens, caps=[int(e) for e in num_edges])
+
+    def dev_push(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, max_nodes, max_edges, d_slots, slot_cap,
+                 d_lens, d_status, stream=None, d_perm=None):
+        _check(lib().ans_dev_joint_polya_wl_push(self.gpu.h, self.loops, self.redraws, self.wl_iter, self.half_iter,
+                                                 num_graphs, _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets),
+                                                 max_nodes, max_edges, _dptr(d_perm) if d_perm is not None else None,
+                                                 _dptr(d_slots), slot_cap, _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_joint_polya_wl_push")
+
+    def dev_pop(self, num_graphs, d_num_nodes, d_edges, d_edge_offsets, d_num_edges, max_nodes, max_edges, d_slots,
+                slot_cap, d_lens, d_status, stream=None):
+        _check(lib().ans_dev_joint_polya_wl_pop(self.gpu.h, self.loops, self.redraws, self.wl_iter, self.half_iter,
+                                                num_graphs, _dptr(d_num_nodes), _dptr(d_edges), _dptr(d_edge_offsets),
+                                                _dptr(d_num_edges), max_nodes, max_edges, _dptr(d_slots), slot_cap,
+                                                _dptr(d_lens), _dptr(d_status), _sptr(stream)),
+               "ans_dev_joint_polya_wl_pop")
 
 
 class _GpuLabelled:

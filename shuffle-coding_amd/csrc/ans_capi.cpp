@@ -14,6 +14,7 @@
 #include "ans_mset.hpp"
 #include "ans_polya.hpp"
 #include "ans_table.hpp"
+#include "ans_joint.hpp"
 #include "ans_wl.hpp"
 
 using namespace shuffle_coding;
@@ -498,6 +499,75 @@ int ans_ar_polya_wl_pop(ans_msg* m, uint32_t num_nodes, int loops, int wl_iter, 
     const uint64_t room = pop_room(num_nodes, cap);
     return graph_pop<wl::PuPop<VecAcc>>(m, nullptr, WlSetting{wl_iter, half_iter}, wl::pu_pop_entries(num_nodes, room, wl_iter),
                                         num_nodes, room, loops, edges, room, num_edges);
+}
+
+// ---- joint shuffle coding of a graph on one message (ans_joint.hpp): ShuffleCodec<JointSliceCodecs<C>,
+// WLOrbitCodecs<JointPrefix<Graph>>> (src/recursive/joint.rs, incomplete.rs:154-187) with C the dense
+// Erdős–Rényi indicator or the ordered Pólya urn.  A failed call puts the message back as it found it.
+extern "C++" {
+namespace {
+void set_bern(joint::ErPush<VecAcc>& s, const ans_table* bern) { s.bern = arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]); }
+void set_bern(joint::ErPop<VecAcc>& s, const ans_table* bern) { s.bern = arer::bern_of(bern->cat.masses[0], bern->cat.masses[1]); }
+void set_bern(joint::PuPush<VecAcc>&, const ans_table*) {}
+void set_bern(joint::PuPop<VecAcc>&, const ans_table*) {}
+template <class St, class Run>
+int joint_host(ans_msg* m, const ans_table* bern, int wl_iter, int half_iter, uint64_t entries, uint32_t num_nodes,
+               uint64_t max_edges, Run&& run) {
+    const Message before = m->m;
+    const int rc = graph_host<St>(m, bern, WlSetting{wl_iter, half_iter}, entries, num_nodes, max_edges, run);
+    if (rc) m->m = before;
+    return rc;
+}
+uint32_t wl_or_0(int wl_iter) { return wl_iter >= 0 && wl_iter <= ANS_WL_MAX_ITER ? wl_iter : 0; }  // (the setting's check refuses the rest)
+}  // namespace
+}  // extern "C++" (templates)
+
+int ans_joint_er_wl_push(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                         const uint32_t* edges, size_t num_edges, uint32_t* perm) {
+    if (!m || !bern || (num_edges && !edges) || num_edges > arer::kMaxEdges) return ANS_E_ARG;
+    using St = joint::ErPush<VecAcc>;
+    return joint_host<St>(m, bern, wl_iter, half_iter, joint::er_push_entries(num_nodes, num_edges, wl_or_0(wl_iter)), num_nodes,
+                          num_edges, [&](auto& c, St& st) {
+                              return joint::push_joint(c, st, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
+                          });
+}
+
+int ans_joint_er_wl_pop(ans_msg* m, const ans_table* bern, uint32_t num_nodes, int loops, int wl_iter, int half_iter,
+                        uint32_t* edges, size_t cap, size_t* num_edges) {
+    if (!m || !bern || !num_edges || (cap && !edges)) return ANS_E_ARG;
+    *num_edges = 0;
+    using St = joint::ErPop<VecAcc>;
+    const uint64_t room = pop_room(num_nodes, cap);
+    return joint_host<St>(m, bern, wl_iter, half_iter, joint::er_pop_entries(num_nodes, room, wl_or_0(wl_iter)), num_nodes, room,
+                          [&](auto& c, St& st) {
+                              uint64_t count = 0;
+                              const int rc = joint::pop_joint(c, st, num_nodes, loops != 0, edges, room, &count);
+                              *num_edges = static_cast<size_t>(count);
+                              return rc;
+                          });
+}
+
+int ans_joint_polya_wl_push(ans_msg* m, uint32_t num_nodes, int loops, int redraws, int wl_iter, int half_iter,
+                            const uint32_t* edges, size_t num_edges, uint32_t* perm) {
+    if (!m || (num_edges && !edges) || num_edges > polya::kMaxEdges) return ANS_E_ARG;
+    using St = joint::PuPush<VecAcc>;
+    return joint_host<St>(m, nullptr, wl_iter, half_iter, joint::pu_push_entries(num_nodes, num_edges, wl_or_0(wl_iter)),
+                          num_nodes, num_edges, [&](auto& c, St& st) {
+                              st.redraws = redraws != 0;
+                              return joint::push_joint(c, st, num_nodes, loops != 0, edges, static_cast<uint32_t>(num_edges), perm);
+                          });
+}
+
+int ans_joint_polya_wl_pop(ans_msg* m, uint32_t num_nodes, int loops, int redraws, int wl_iter, int half_iter,
+                           uint32_t* edges, size_t num_edges) {
+    if (!m || (num_edges && !edges) || num_edges > polya::kMaxEdges) return ANS_E_ARG;
+    using St = joint::PuPop<VecAcc>;
+    return joint_host<St>(m, nullptr, wl_iter, half_iter, joint::pu_pop_entries(num_nodes, num_edges, wl_or_0(wl_iter)), num_nodes,
+                          num_edges, [&](auto& c, St& st) {
+                              st.redraws = redraws != 0;
+                              uint64_t count = 0;
+                              return joint::pop_joint(c, st, num_nodes, loops != 0, edges, num_edges, &count);
+                          });
 }
 
 // ---- ... of a graph with node and edge labels (Graph<N, E, Undirected>, N and E each usize or ();

@@ -719,6 +719,10 @@ int ans_gpu_last_launch(const ans_gpu* g, char* buf, size_t cap, size_t* len) tr
         case kRecArerWllPop: w = std::snprintf(o, room - 1, "k_arer_wll_pop(wl_iter=%d,half_iter=%d,node=%d,edge=%d)", a[0], a[2], a[3], a[4]); break;
         case kRecArpuWllPush: w = std::snprintf(o, room - 1, "k_arpu_wll_push(wl_iter=%d,half_iter=%d,node=%d,edge=%d)", a[0], a[2], a[3], a[4]); break;
         case kRecArpuWllPop: w = std::snprintf(o, room - 1, "k_arpu_wll_pop(wl_iter=%d,half_iter=%d,node=%d,edge=%d)", a[0], a[2], a[3], a[4]); break;
+        case kRecJointErPush: w = std::snprintf(o, room - 1, "k_joint_er_push(wl_iter=%d,half_iter=%d)", a[0], a[2]); break;
+        case kRecJointErPop: w = std::snprintf(o, room - 1, "k_joint_er_pop(wl_iter=%d,half_iter=%d)", a[0], a[2]); break;
+        case kRecJointPuPush: w = std::snprintf(o, room - 1, "k_joint_pu_push(wl_iter=%d,half_iter=%d,redraws=%d)", a[0], a[2], a[3]); break;
+        case kRecJointPuPop: w = std::snprintf(o, room - 1, "k_joint_pu_pop(wl_iter=%d,half_iter=%d,redraws=%d)", a[0], a[2], a[3]); break;
         default: w = std::snprintf(o, room - 1, "?"); break;
         }
         at += static_cast<size_t>(w);

@@ -40,6 +40,10 @@ enum LaunchKind : uint8_t {
     kRecArerWllPop,     //   a = {wl_iter, workgroups, half_iter, node labels, edge labels}
     kRecArpuWllPush,
     kRecArpuWllPop,
+    kRecJointErPush,    // k_joint_er_push / _pop, k_joint_pu_push / _pop (ans_joint.hip)
+    kRecJointErPop,     //   a = {wl_iter, workgroups, half_iter, redraws (the urn's)}
+    kRecJointPuPush,
+    kRecJointPuPop,
 };
 struct LaunchRec {
     uint8_t kind;
@@ -49,7 +53,7 @@ struct LaunchRec {
 // The slot of a[] in which a record kind keeps its launch's workgroup count (ans_gpu_last_launch_grid
 // reads it; the text of ans_gpu_last_launch does not show it), or -1 for a kind that keeps none.
 constexpr int rec_grid_slot(uint8_t kind) {
-    return kind >= kRecMsetPush && kind <= kRecArpuWllPop ? 1 : -1;
+    return kind >= kRecMsetPush && kind <= kRecJointPuPop ? 1 : -1;
 }
 // ... and the count as the slot holds it: the workspace forms launch at most 8 workgroups per CU;
 // the LDS form of the multiset kernels, one lane per chunk, can pass an int16_t and saturates.
